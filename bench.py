@@ -16,10 +16,19 @@ every rank serves the same query batch, one RCCL all-gather of [B,k]
 CPU cpu_topk_merge_sharded, helper.h:137-167). value = queries/s of the
 whole job over the N x 10M corpus.
 
-Emits ONE JSON line from rank 0 including `roofline` (HIP-event time +
-algorithmic bytes of the list-scan kernel vs 8 TB/s HBM peak) and
+A plain run does only what the headline figure needs: build the index, warm
+up, time `--steps` steps, and emit ONE JSON line from rank 0 (`value`,
+`ms_per_step`, ...). `--dump-outputs DIR` also writes what the last timed
+step returned (`ids.npy` as float64, `dists.npy` as float32, [batch, k]); the
+inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds everything else to the same line: the recall@k gate against
+exact ground truth (with the fall-back to the exact one-pass scan when the
+two-stage scan misses it), `roofline` (HIP-event time + algorithmic bytes of
+the list-scan kernel vs 8 TB/s HBM peak, from a short unpipelined probe) and
 `cpu_baseline` (the oracle CPU port of the reference probe, OpenMP, timed on
-a bounded sample of the same workload).
+a bounded sample of the same workload). Without `--full` those fields are
+null.
 """
 
 import argparse
@@ -91,7 +100,14 @@ def kmeans_torch(data_gpu: torch.Tensor, nlist: int, iters: int, seed: int):
         a = d2.argmin(1)
         cent_new = torch.zeros_like(cent)
         counts = torch.zeros(nlist, device=cent.device, dtype=torch.float32)
-        cent_new.index_add_(0, a, sample)
+        # the f32 centroid sums must not depend on atomic-add order, or the
+        # index (and so --dump-outputs) would differ from run to run
+        det = torch.are_deterministic_algorithms_enabled()
+        torch.use_deterministic_algorithms(True)
+        try:
+            cent_new.index_add_(0, a, sample)
+        finally:
+            torch.use_deterministic_algorithms(det)
         counts.index_add_(0, a, torch.ones_like(a, dtype=torch.float32))
         empty = counts == 0
         counts = counts.clamp(min=1.0)
@@ -99,7 +115,7 @@ def kmeans_torch(data_gpu: torch.Tensor, nlist: int, iters: int, seed: int):
         if empty.any():
             # reseed empty lists from random sample rows
             ridx = torch.randint(0, sample.shape[0], (int(empty.sum()),),
-                                 device=cent.device)
+                                 generator=g).to(cent.device)
             cent[empty] = sample[ridx]
     return cent.contiguous()
 
@@ -165,6 +181,63 @@ def run_cpu_baseline(host_vecs: np.ndarray, cent: np.ndarray,
     }
 
 
+def measure_roofline(ix, step, args, world, pipeline):
+    """--full: list-scan kernel roofline from the index's HIP-event perf
+    counters. Under pipelining, concurrent streams share bandwidth and the
+    event windows stretch past the kernels' standalone durations, so the
+    kernel windows are re-measured with a short UNPIPELINED probe; without
+    pipelining the counters of the timed steps are used as they are."""
+    perf = ix.perf()
+    kdiv = args.steps
+    if pipeline:
+        ix.perf_reset()
+        kdiv = 3
+        for i in range(kdiv):
+            step(i)
+        perf = ix.perf()
+    log(f"[bench] perf: rank {perf['rank_ms']/kdiv:.3f} ms/step, "
+        f"scan {perf['scan_ms']/kdiv:.3f}, "
+        f"other {perf.get('other_ms', 0.0)/kdiv:.3f}, "
+        f"select {perf['select_ms']/kdiv:.3f}")
+    # first-pass scan element size: the refine mode's first pass reads the
+    # internal byte image regardless of the (f32) storage dtype
+    elem = 1 if args.refine else {"f32": 4, "f16": 2,
+                                  "bf16": 2}.get(args.qtype, 1)
+    scan_gbs = (perf["scan_bytes"] / 4 * elem / 1e9) / max(
+        perf["scan_ms"] / 1e3, 1e-9)
+    # PMC traffic: per-launch HBM bytes measured with rocprofv3 --pmc
+    # FETCH_SIZE against THIS workload+scan mode, committed under profiles/
+    # (collected by tools/collect_traffic.py, which applies the x2 gfx950
+    # counter correction). Emitted only when the keyed entry matches the
+    # exact configuration being run; otherwise null.
+    traffic = None
+    traffic_src = None
+    try:
+        tpath = os.path.join(REPO, "profiles", "r02_traffic.json")
+        with open(tpath) as f:
+            tdb = json.load(f)
+        key = (f"{args.rows}x{args.dim}-nlist{args.nlist}-"
+               f"nprobe{args.nprobe}-batch{args.batch}-"
+               f"{'refine' if args.refine else 'exact'}-{args.qtype}")
+        ent = tdb.get(key)
+        if ent and world == 1:
+            traffic = ent["bytes_per_launch"]
+            traffic_src = ent.get("provenance")
+    except Exception:
+        pass
+    roofline = {
+        "bound": "hbm",
+        "achieved": round(scan_gbs, 1),
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": round(scan_gbs / HBM_PEAK_GBS, 4),
+        "traffic": traffic,
+    }
+    if traffic_src:
+        roofline["traffic_provenance"] = traffic_src
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -180,6 +253,14 @@ def main():
     ap.add_argument("--recall-queries", type=int, default=256)
     ap.add_argument("--cpu-baseline-queries", type=int, default=48)
     ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the recall gate, the roofline probe and "
+                         "the CPU baseline (a plain run only builds, warms "
+                         "up, times the steps and reports)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed "
+                         "step returned to DIR/ids.npy (float64) and "
+                         "DIR/dists.npy (float32)")
     ap.add_argument("--refine", type=int, default=64,
                     help="two-stage scan: byte first pass + exact f32 "
                          "re-rank of the top-R (0 = exact one-pass scan). "
@@ -190,13 +271,16 @@ def main():
                          "fails with refine on, the bench falls back to "
                          "the exact one-pass scan and re-measures — the "
                          "reported configuration always satisfies the "
-                         "gate if the exact path does")
+                         "gate if the exact path does (the gate runs "
+                         "under --full only)")
     ap.add_argument("--qtype", default="f32",
                     choices=["f32", "f16", "bf16", "int8", "uint8"],
                     help="storage type; the BASELINE metric is f32 — narrow "
                          "runs are secondary datapoints and report their own "
                          "dtype")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -231,7 +315,8 @@ def main():
     # keep a full host copy only where the CPU baseline will need it
     # (rank 0, N=1); otherwise stream 2M-row chunks through a small host
     # buffer so an 8-rank run never stages 8 x 30 GB in host RAM at once.
-    need_host = (rank == 0 and world == 1 and not args.skip_cpu_baseline)
+    need_host = (args.full and rank == 0 and world == 1
+                 and not args.skip_cpu_baseline)
     host_vecs = data.cpu().numpy() if need_host else None
     ix = engine.IvfFlatIndex(args.dim, args.nlist, metric="l2sq",
                              capacity=args.rows, device=devno,
@@ -260,9 +345,10 @@ def main():
         args.refine = 0
     log(f"[bench] build done in {time.perf_counter() - t_build0:.1f}s")
 
-    # ---- recall check ------------------------------------------------------
+    # ---- recall check (--full) ---------------------------------------------
     nrq = args.recall_queries
-    gt_local = exact_gt(data, queries[:nrq], args.k)  # local-shard GT
+    gt_local = (exact_gt(data, queries[:nrq], args.k)  # local-shard GT
+                if args.full else None)
 
     def measure_recall():
         ids_r, dists_r = ix.search_device(queries[:nrq].contiguous(),
@@ -287,9 +373,11 @@ def main():
             len(set(m_ids[i]).intersection(g_ids[i])) / args.k
             for i in range(nrq)]))
 
-    recall = measure_recall()
-    log(f"[bench] recall@{args.k} = {recall:.4f} (target >= 0.95)")
-    if recall < 0.95 and args.refine:
+    recall = None
+    if args.full:
+        recall = measure_recall()
+        log(f"[bench] recall@{args.k} = {recall:.4f} (target >= 0.95)")
+    if args.full and recall < 0.95 and args.refine:
         # two-stage scan missed the gate on this data: fall back to the
         # exact one-pass scan and re-measure. recall is identical on every
         # rank (deterministic merged value), so all ranks take this branch
@@ -321,7 +409,7 @@ def main():
             off = rank * args.rows
             ids = np.where(ids >= 0, ids + off, -1)
             ids, dists = allgather_merge(ids, dists, args.k)
-        return ids
+        return ids, dists
 
     def step(i):
         b0 = (i % nbatches) * args.batch
@@ -330,18 +418,21 @@ def main():
         return merge(ids, dists)
 
     def run_steps(n):
+        """Runs n steps; returns what the last one computed."""
+        out = None
         if n <= 0:
-            return
+            return out
         if not pipeline:
             for i in range(n):
-                step(i)
-            return
+                out = step(i)
+            return out
         t = submit(0)
         for i in range(n):
             nxt = submit(i + 1) if i + 1 < n else None
             ids, dists = ix.search_collect(t)
-            merge(ids, dists)
+            out = merge(ids, dists)
             t = nxt
+        return out
 
     run_steps(args.warmup)
     ix.perf_reset()
@@ -350,7 +441,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last_ids, last_dists = run_steps(args.steps)
     torch.cuda.synchronize()
     if distributed:
         import torch.distributed as dist
@@ -364,76 +455,32 @@ def main():
         elapsed = float(t.item())
 
     qps = args.steps * args.batch / elapsed
-    perf = ix.perf()
-    # Under pipelining, concurrent streams share bandwidth and the event
-    # windows stretch past the kernels' standalone durations; re-measure the
-    # kernel windows with a short UNPIPELINED probe so the roofline reflects
-    # the kernel itself. Step throughput (elapsed) stays pipelined.
-    nprobe_steps = 0
-    if pipeline:
-        ix.perf_reset()
-        nprobe_steps = 3
-        for i in range(nprobe_steps):
-            step(i)
-        perf = ix.perf()
-        kdiv = nprobe_steps
-    else:
-        kdiv = args.steps
-    log(f"[bench] perf: rank {perf['rank_ms']/kdiv:.3f} ms/step, "
-        f"scan {perf['scan_ms']/kdiv:.3f}, "
-        f"other {perf.get('other_ms', 0.0)/kdiv:.3f}, "
-        f"select {perf['select_ms']/kdiv:.3f}, "
-        f"step total {elapsed/args.steps*1e3:.3f} (pipelined={pipeline})")
+    log(f"[bench] step total {elapsed/args.steps*1e3:.3f} ms "
+        f"(pipelined={pipeline})")
 
-    # ---- roofline (list-scan kernel, HIP events on the index stream) ------
-    # first-pass scan element size: the refine mode's first pass reads the
-    # internal byte image regardless of the (f32) storage dtype
-    elem = 1 if args.refine else {"f32": 4, "f16": 2,
-                                  "bf16": 2}.get(args.qtype, 1)
-    scan_gbs = (perf["scan_bytes"] / 4 * elem / 1e9) / max(
-        perf["scan_ms"] / 1e3, 1e-9)
-    # PMC traffic: per-launch HBM bytes measured with rocprofv3 --pmc
-    # FETCH_SIZE against THIS workload+scan mode, committed under profiles/
-    # (collected by tools/collect_traffic.sh; x2 gfx950 counter correction
-    # per MI355X_MICROARCH.md). Emitted only when the keyed entry matches
-    # the exact configuration being run; otherwise null.
-    traffic = None
-    traffic_src = None
-    try:
-        tpath = os.path.join(REPO, "profiles", "r02_traffic.json")
-        with open(tpath) as f:
-            tdb = json.load(f)
-        key = (f"{args.rows}x{args.dim}-nlist{args.nlist}-"
-               f"nprobe{args.nprobe}-batch{args.batch}-"
-               f"{'refine' if args.refine else 'exact'}-{args.qtype}")
-        ent = tdb.get(key)
-        if ent and world == 1:
-            traffic = ent["bytes_per_launch"]
-            traffic_src = ent.get("provenance")
-    except Exception:
-        pass
-    roofline = {
-        "bound": "hbm",
-        "achieved": round(scan_gbs, 1),
-        "peak": HBM_PEAK_GBS,
-        "unit": "GB/s",
-        "frac": round(scan_gbs / HBM_PEAK_GBS, 4),
-        "traffic": traffic,
-    }
-    if traffic_src:
-        roofline["traffic_provenance"] = traffic_src
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path received from the last timed step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ids.npy"),
+                np.asarray(last_ids).astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "dists.npy"),
+                np.asarray(last_dists).astype(np.float32))
 
-    # ---- CPU baseline (rank 0, N=1 only) -----------------------------------
+    roofline = None
     cpu_baseline = None
-    if host_vecs is not None:
-        log("[bench] CPU baseline (oracle port, OpenMP) ...")
-        try:
-            cpu_baseline = run_cpu_baseline(
-                host_vecs, cent_np, assign_np,
-                queries_host.numpy(), args.nprobe, args.k,
-                args.cpu_baseline_queries)
-        except Exception as e:  # report the miss, never fake a number
-            log(f"[bench] cpu_baseline failed: {e}")
+    if args.full:
+        roofline = measure_roofline(ix, step, args, world, pipeline)
+
+        # ---- CPU baseline (rank 0, N=1 only) -------------------------------
+        if host_vecs is not None:
+            log("[bench] CPU baseline (oracle port, OpenMP) ...")
+            try:
+                cpu_baseline = run_cpu_baseline(
+                    host_vecs, cent_np, assign_np,
+                    queries_host.numpy(), args.nprobe, args.k,
+                    args.cpu_baseline_queries)
+            except Exception as e:  # report the miss, never fake a number
+                log(f"[bench] cpu_baseline failed: {e}")
 
     if rank == 0:
         line = {
@@ -459,7 +506,8 @@ def main():
                 "nprobe": args.nprobe,
                 "global_batch": args.batch,
                 "k": args.k,
-                "recall_at_k": round(recall, 4),
+                "recall_at_k": (round(recall, 4) if recall is not None
+                                else None),
                 "scan": (f"two-stage-refine-R{args.refine}" if args.refine
                          else "exact-one-pass"),
                 "parallelism": f"sharded-lists x{world}" if world > 1

@@ -34,6 +34,14 @@ KIND_SORTED64 = 4
 _lib = None
 
 
+def ref_available() -> bool:
+    """True when the reference's compiled filters can be loaded. Without
+    them the build_* functions below serialize the same payload formats in
+    python (py_build_*), so callers that only need a valid payload run from
+    the repository alone."""
+    return os.path.exists(_REF)
+
+
 def ref_lib():
     global _lib
     if _lib is None:
@@ -83,6 +91,8 @@ def build_bloom(keys: np.ndarray, nbits: int, k: int, seed: int) -> bytes:
     """bloomfilter_init_with_seed + add(key8) per key; payload = the flat
     bloomfilter_t bytes (header 24 B + bitmap). nbits is rounded up to a
     power of two by the reference (bloom.c:96-118)."""
+    if not ref_available():
+        return py_build_bloom(keys, nbits, k, seed)
     L = ref_lib()
     bf = L.bloomfilter_init_with_seed(nbits, k, seed)
     assert bf
@@ -114,6 +124,8 @@ def ref_bloom_test(payload: bytes, keys: np.ndarray) -> np.ndarray:
 
 def build_cbitmap(keys: np.ndarray, use_offset: bool = True,
                   max_bits: int = 1 << 32) -> bytes:
+    if not ref_available():
+        return py_build_cbitmap(keys, use_offset, max_bits)
     L = ref_lib()
     keys = np.ascontiguousarray(keys, dtype=np.uint64)
     out = ct.c_void_p()
@@ -128,6 +140,8 @@ def build_cbitmap(keys: np.ndarray, use_offset: bool = True,
 
 
 def build_croaring(keys: np.ndarray, run_optimize: bool = True) -> bytes:
+    if not ref_available():
+        return py_build_croaring(keys)
     L = ref_lib()
     keys = np.ascontiguousarray(keys, dtype=np.uint64)
     r = L.mo_croaring_create()
@@ -180,6 +194,93 @@ def ref_contains(kind: int, payload: bytes, keys: np.ndarray) -> np.ndarray:
         L.mo_croaring_free(h)
         return out
     raise ValueError(kind)
+
+
+# ---------------- python serializers (spec-level) ---------------------------
+
+def py_build_bloom(keys: np.ndarray, nbits: int, k: int, seed: int) -> bytes:
+    """The bloomfilter_t layout {"XXBF", k u32, nbits u64, seed u64, bitmap}
+    with nbits rounded up to a power of two and the probes of
+    py_bloom_test set for every key."""
+    import xxhash
+    real = 64
+    while real < nbits:
+        real <<= 1
+    words = np.zeros(real // 64, dtype=np.uint64)
+    for kk in np.ascontiguousarray(keys, dtype=np.int64):
+        h = xxhash.xxh3_128(int(kk).to_bytes(8, "little", signed=True),
+                            seed=seed).intdigest()
+        h1, h2 = h & (2**64 - 1), h >> 64
+        for j in range(k):
+            pos = (h1 + j * h2) & (real - 1)
+            words[pos >> 6] |= np.uint64(1 << (pos & 63))
+    return (b"XXBF" + np.uint32(k).tobytes() + np.uint64(real).tobytes()
+            + np.uint64(seed & (2**64 - 1)).tobytes() + words.tobytes())
+
+
+def py_build_cbitmap(keys: np.ndarray, use_offset: bool = True,
+                     max_bits: int = 1 << 32) -> bytes:
+    """[base u64][nbits u64][words]: bit i is value base + i; base is the
+    smallest key rounded down to a word (0 in the legacy layout)."""
+    vals = np.unique(np.ascontiguousarray(keys, dtype=np.uint64))
+    if len(vals) == 0:
+        return np.zeros(2, dtype=np.uint64).tobytes()
+    base = (int(vals[0]) // 64) * 64 if use_offset else 0
+    nbits = ((int(vals[-1]) - base) // 64 + 1) * 64
+    if nbits > max_bits:
+        raise ValueError(f"cbitmap span {nbits} exceeds max_bits {max_bits}")
+    bits = (vals - np.uint64(base)).astype(np.int64)
+    words = np.zeros(nbits // 64, dtype=np.uint64)
+    np.bitwise_or.at(words, bits >> 6,
+                     np.uint64(1) << (bits & 63).astype(np.uint64))
+    return (np.array([base, nbits], dtype=np.uint64).tobytes()
+            + words.tobytes())
+
+
+def _py_roaring32(vals: np.ndarray) -> bytes:
+    """Portable roaring32 (RoaringFormatSpec) without run containers: cookie
+    12346, container count, (key, cardinality - 1) pairs, offset table, then
+    sorted u16 arrays (cardinality <= 4096) or 8 KiB bitsets."""
+    hi = (vals >> np.uint32(16)).astype(np.uint16)
+    lo = (vals & np.uint32(0xFFFF)).astype(np.uint16)
+    ckeys, starts = np.unique(hi, return_index=True)
+    ends = list(starts[1:]) + [len(vals)]
+    bodies = []
+    for a, b in zip(starts, ends):
+        part = lo[a:b]
+        if len(part) <= 4096:
+            bodies.append(part.astype("<u2").tobytes())
+        else:
+            bs = np.zeros(8192, dtype=np.uint8)
+            np.bitwise_or.at(bs, part >> 3,
+                             np.uint8(1) << (part & 7).astype(np.uint8))
+            bodies.append(bs.tobytes())
+    n = len(ckeys)
+    head = np.array([12346, n], dtype="<u4").tobytes()
+    desc = np.empty((n, 2), dtype="<u2")
+    desc[:, 0] = ckeys
+    desc[:, 1] = np.array([b - a - 1 for a, b in zip(starts, ends)])
+    offs, pos = [], 8 + 8 * n
+    for body in bodies:
+        offs.append(pos)
+        pos += len(body)
+    return (head + desc.tobytes() + np.array(offs, dtype="<u4").tobytes()
+            + b"".join(bodies))
+
+
+def py_build_croaring(keys: np.ndarray) -> bytes:
+    """roaring64 PORTABLE bytes: u64 bucket count, then per bucket the high
+    32 bits (u32) and a portable roaring32 of the low 32 bits."""
+    vals = np.unique(np.ascontiguousarray(keys, dtype=np.uint64))
+    high = (vals >> np.uint64(32)).astype(np.uint32)
+    low = (vals & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    buckets, starts = np.unique(high, return_index=True)
+    ends = list(starts[1:]) + [len(vals)]
+    out = [np.uint64(len(buckets)).tobytes()]
+    for bkey, a, b in zip(buckets, starts, ends):
+        out.append(np.uint32(bkey).tobytes())
+        out.append(_py_roaring32(low[a:b]))
+    return b"".join(out)
 
 
 # ---------------- python restatements (spec-level) --------------------------

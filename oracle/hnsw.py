@@ -4,7 +4,9 @@ HNSW parity tooling: (a) ctypes driver for oracle/_ref/libref_hnsw.so — the
 reference's own usearch 2.25.3 engine (build / search / graph export), and
 (b) a numpy restatement of usearch's search algorithm over the exported
 graph, pinned against (a). The GPU product kernel is parity-tested against
-both on the SAME exported graph.
+both on the SAME exported graph. Where the usearch sources are not available
+(a plain checkout), (a) is served by oracle/hnsw_engine.c instead: usearch's
+build, search and file format restated in plain C behind the same C ABI.
 
 Algorithm restated from the vendored usearch-2.25.3 index.hpp:
   - search entry (index.hpp:3455-3498): greedy descent `search_for_one_`
@@ -44,12 +46,18 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
+        # the usearch-backed shim where it has been built; otherwise the
+        # in-repository engine (hnsw_engine.c: usearch's build and search
+        # restated in plain C behind the same ABI)
         path = os.path.join(_HERE, "_ref", "libref_hnsw.so")
         if not os.path.exists(path):
-            import subprocess
-            subprocess.run(["make", "-s", "hnsw_shim"], cwd=_HERE, check=True)
+            path = os.path.join(_HERE, "libhnsw_engine.so")
         if not os.path.exists(path):
-            raise RuntimeError("oracle/_ref/libref_hnsw.so unavailable")
+            import subprocess
+            subprocess.run(["make", "-s", "libhnsw_engine.so"], cwd=_HERE,
+                           check=True)
+        if not os.path.exists(path):
+            raise RuntimeError("oracle/libhnsw_engine.so unavailable")
         L = ct.CDLL(path)
         L.ref_hnsw_create.restype = ct.c_void_p
         L.ref_hnsw_create.argtypes = [ct.c_size_t, ct.c_int, ct.c_size_t,

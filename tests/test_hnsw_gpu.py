@@ -1,7 +1,8 @@
 """GPU parity: the CDNA4 HNSW beam-search kernel vs the numpy oracle
 restatement AND usearch's own results, all on the SAME exported graph.
-Requires a real MI355X (`-m gpu`); builds the usearch graph live via the
-prebuilt oracle/_ref/libref_hnsw.so that travels with the repo."""
+Requires a real MI355X (`-m gpu`); builds the graph live with the reference
+engine oracle/hnsw.py loads: usearch itself where oracle/_ref has been
+built, otherwise the in-repository restatement (oracle/hnsw_engine.c)."""
 
 import numpy as np
 import pytest

@@ -8,11 +8,11 @@ with trace domains); FETCH_SIZE is reported in KiB units per dispatch and
 under-reports wide coalesced streaming reads by 2x on gfx950 — the x2
 correction is applied here and stated in the provenance.
 
-Run ON A GPU BOX (gpurun):
-  cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-  rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc -o traffic \
-      -- python bench.py --steps 3 --warmup 1 --skip-cpu-baseline ...
-  python tools/collect_traffic.py gpurun_out/pmc/*/traffic_counter_collection.csv \
+Run on a machine with the GPU (a plain bench run launches the scan kernel
+often enough; `--full` is not needed):
+  rocprofv3 --pmc FETCH_SIZE -d pmc_out -o traffic \
+      -- python bench.py --steps 3 --warmup 1 ...
+  python tools/collect_traffic.py pmc_out/*/traffic_counter_collection.csv \
       --key "10000000x768-nlist4096-nprobe32-batch1024-refine-f32" \
       --kernel scan_i8_dot --out profiles/r02_traffic.json
 """
