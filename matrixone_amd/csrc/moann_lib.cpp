@@ -545,7 +545,14 @@ std::unique_ptr<Result> run_search(IvfIndex* ix, const float* queries,
     const int qt_rank = pick_qt(ix->kmetric, ix->dpad,
                                 ix->qtype != Quantization_F32 ||
                                     refine_scan);
-    const int qt = byte_dot16 ? 16 : qt_rank;
+    /* The byte list scan has exactly two tile widths (dot-form 16, and 8 for
+     * both the dot-form and the uchar4 kernel). qt_rank is sized for F32
+     * query tiles in LDS and drops to 4 above dpad 1663 — a width no byte
+     * kernel has (launch_scan_i8 rejects it), while 8 byte rows of any
+     * supported dpad fit LDS with room to spare. */
+    const bool byte_scan = refine_scan ||
+                           (ix->qtype != Quantization_F32 && !half_st);
+    const int qt = byte_dot16 ? 16 : (byte_scan ? 8 : qt_rank);
     if (use_mfma_rank) {
         cx->w_cdists.ensure((size_t)nq * ix->nlist * 4);
         HIP_CHECK(hipEventRecord(cx->ev[0], s));

@@ -372,6 +372,36 @@ def test_quantized_storage_padded_dim():
     ix.close()
 
 
+@pytest.mark.parametrize("d", [1700, 3072])
+def test_quantized_storage_wide_dim(d):
+    """int8 storage above dpad 1663, where the f32 rank stage's tile width
+    drops to 4: the byte list scan keeps its own width of 8 (uchar4 kernel
+    at d=1700, dpad % 16 != 0; dot form at d=3072, past the QT=16 LDS
+    limit). Tiles of 8 plus a tail: 19 queries on every list."""
+    from matrixone_amd import engine
+    rng = np.random.Generator(np.random.PCG64(920 + d))
+    n, nlist, nq, k = 1500, 4, 19, 10
+    vecs = rng.standard_normal((n, d), dtype=np.float32)
+    cents = vecs[rng.choice(n, nlist, replace=False)].copy()
+    assign = rng.integers(0, nlist, n)
+    queries = rng.standard_normal((nq, d), dtype=np.float32)
+    vmin, vmax = float(vecs.min()), float(vecs.max())
+    mul, add = orc.int8_params(vmin, vmax)
+    idx = orc.IvfIndex(cents, vecs, assign)
+    ref_ids, ref_d = orc.ivf_search_quantized(
+        idx, orc.METRIC_L2SQ, queries, nlist, k, mul, add)
+    ix = engine.IvfFlatIndex(d, nlist, metric="l2sq", capacity=n,
+                             qtype="int8")
+    ix.add(vecs)
+    ix.set_centroids(cents)
+    ix.set_assignments(assign.astype(np.int32))
+    ix.set_quantizer(vmin, vmax)
+    ix.build()
+    ids, dists = ix.search(queries, k, nlist)
+    ix.close()
+    _assert_parity(ids, dists, ref_ids, ref_d, ctx=f"int8-l2sq-d{d}")
+
+
 def test_asm768_scan_parity():
     """The hand-scheduled d=768 L2 asm kernel (scan_asm768.hip, the default
     path for the flagship shape): results == oracle on ragged lists (rows not

@@ -94,7 +94,9 @@ def main():
     print(f"[diag] k={k} ids == first {k} of k=R ids: {agree:.4f}")
 
     # torch replication of the byte image (enable_refine's quantile recipe)
-    rows_f32 = data  # slot order == add order
+    # ADD order. The product's slots are list-major, so above 131072 rows it
+    # samples other rows for its quantiles than this does (lo/hi differ a bit).
+    rows_f32 = data
     ns = min(args.rows, 131072)
     samp = rows_f32[:ns].reshape(-1)
     nlo = samp.numel() // 1000
