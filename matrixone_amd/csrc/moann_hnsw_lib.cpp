@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "../../include/moann.h"
-#include "moann_internal.h"
+#include "moann_host_common.h"
 
 namespace moann {
 void launch_hnsw_search(int metric, const float* vecs, int dpad, int64_t n,
@@ -36,37 +36,7 @@ namespace {
 
 using namespace moann;
 
-#define HIP_CHECK(expr)                                                     \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess)                                               \
-            throw std::runtime_error(std::string("HIP error: ") +           \
-                                     hipGetErrorString(_e) + " at " #expr); \
-    } while (0)
-
-void hn_set_errmsg(void* errmsg, const char* context, const char* message) {
-    if (!errmsg) return;
-    std::string full = std::string(context) + ": " + message;
-    *(char**)errmsg = strdup(full.c_str());
-}
-
-struct HnswDevBuf {
-    void* ptr = nullptr;
-    size_t bytes = 0;
-    void ensure(size_t need) {
-        if (need <= bytes) return;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-        HIP_CHECK(hipMalloc(&ptr, need));
-        bytes = need;
-    }
-    ~HnswDevBuf() {
-        if (ptr) (void)hipFree(ptr);
-    }
-    template <typename T>
-    T* as() { return (T*)ptr; }
-};
+#define HIP_CHECK MOANN_HIP_CHECK /* local short name */
 
 struct HnswIndex {
     int device = 0;
@@ -91,7 +61,7 @@ struct HnswIndex {
     std::vector<int64_t> h_keys; /* slot -> key, for docfilter bitsets */
     uint32_t default_ef = 64;    /* moann_hnsw_set_ef (usearchex entry) */
 
-    HnswDevBuf w_queries, w_qnorms, w_visited, w_out_ids, w_out_dists,
+    MoannDevBuf w_queries, w_qnorms, w_visited, w_out_ids, w_out_dists,
         w_evals, w_filter;
 
     std::mutex mu;
@@ -133,14 +103,8 @@ void run_hnsw_search(HnswIndex* ix, const float* queries, bool on_device,
         ix->ev_made = true;
     }
 
-    ix->w_queries.ensure((size_t)nq * dpad * 4);
-    if ((int)ix->dim != dpad)
-        HIP_CHECK(hipMemsetAsync(ix->w_queries.ptr, 0, (size_t)nq * dpad * 4, s));
-    HIP_CHECK(hipMemcpy2DAsync(ix->w_queries.ptr, (size_t)dpad * 4, queries,
-                               (size_t)ix->dim * 4, (size_t)ix->dim * 4, nq,
-                               on_device ? hipMemcpyDeviceToDevice
-                                         : hipMemcpyHostToDevice, s));
-    const float* d_q = ix->w_queries.as<float>();
+    const float* d_q = stage_padded_queries(ix->w_queries, queries, on_device,
+                                            nq, ix->dim, ix->dpad, s);
     const float* d_qn = nullptr;
     if (ix->metric == 2) {
         ix->w_qnorms.ensure(nq * 4);
@@ -228,7 +192,7 @@ moann_hnsw_c moann_hnsw_new(uint32_t dimension, int usearch_metric,
         ix->max_level = max_level;
         return (moann_hnsw_c)ix.release();
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_new", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_new", e.what());
         return nullptr;
     }
 }
@@ -245,7 +209,7 @@ void moann_hnsw_set_vectors(moann_hnsw_c h, const float* vecs, void* errmsg) {
                               hipMemcpyHostToDevice));
         ix->have_vecs = true;
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_set_vectors", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_set_vectors", e.what());
     }
 }
 
@@ -258,7 +222,7 @@ void moann_hnsw_set_keys(moann_hnsw_c h, const int64_t* keys, void* errmsg) {
                             hipMemcpyHostToDevice));
         ix->h_keys.assign(keys, keys + ix->n);
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_set_keys", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_set_keys", e.what());
     }
 }
 
@@ -281,7 +245,7 @@ void moann_hnsw_set_level0(moann_hnsw_c h, const int64_t* offs,
         ix->maxdeg = std::max(ix->maxdeg, maxdeg);
         ix->have_l0 = true;
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_set_level0", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_set_level0", e.what());
     }
 }
 
@@ -308,7 +272,7 @@ void moann_hnsw_set_upper(moann_hnsw_c h, const int32_t* u_idx,
                                 hipMemcpyHostToDevice));
         ix->have_upper = true;
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_set_upper", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_set_upper", e.what());
     }
 }
 
@@ -327,7 +291,7 @@ void moann_hnsw_build(moann_hnsw_c h, void* errmsg) {
         }
         ix->built = true;
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_build", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_build", e.what());
     }
 }
 
@@ -339,7 +303,7 @@ void moann_hnsw_search(moann_hnsw_c h, const float* queries, uint64_t nq,
         if (dim != ix->dim) throw std::runtime_error("query dim mismatch");
         run_hnsw_search(ix, queries, false, nq, ef, k, out_keys, out_dists);
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_search", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_search", e.what());
     }
 }
 
@@ -353,7 +317,7 @@ void moann_hnsw_search_device(moann_hnsw_c h, const void* queries_dev,
         run_hnsw_search(ix, (const float*)queries_dev, true, nq, ef, k,
                         out_keys, out_dists);
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_search_device", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_search_device", e.what());
     }
 }
 
@@ -375,7 +339,7 @@ void moann_hnsw_search_filtered(moann_hnsw_c h, const float* queries,
         run_hnsw_search(ix, queries, false, nq, ef, k, out_keys, out_dists,
                         slot_bitset);
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_search_filtered", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_search_filtered", e.what());
     }
 }
 
@@ -384,7 +348,7 @@ void moann_hnsw_set_ef(moann_hnsw_c h, uint32_t ef, void* errmsg) {
         if (ef == 0) throw std::runtime_error("ef must be positive");
         HX(h)->default_ef = ef;
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_set_ef", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_set_ef", e.what());
     }
 }
 
@@ -456,7 +420,7 @@ void moann_hnsw_destroy(moann_hnsw_c h, void* errmsg) {
     try {
         delete HX(h);
     } catch (const std::exception& e) {
-        hn_set_errmsg(errmsg, "moann_hnsw_destroy", e.what());
+        moann_set_errmsg(errmsg, "moann_hnsw_destroy", e.what());
     }
 }
 

@@ -10,7 +10,11 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
+
+#include "moann_internal.h"  /* ScanJobs */
+#include "moann_scan_plan.h" /* HostScanJobs */
 
 namespace moann {
 
@@ -76,6 +80,56 @@ struct MoannDevBuf {
     template <typename T>
     T* as() { return (T*)ptr; }
 };
+
+/* Grow `buf` to fit a host vector and enqueue its H2D copy; the vector must
+ * stay untouched until the copy has run. */
+template <typename T>
+inline void upload_vector(MoannDevBuf& buf, const std::vector<T>& v,
+                          hipStream_t s) {
+    buf.ensure(v.size() * sizeof(T));
+    MOANN_HIP_CHECK(hipMemcpyAsync(buf.ptr, v.data(), v.size() * sizeof(T),
+                                   hipMemcpyHostToDevice, s));
+}
+
+/* Queries to the device as [nq][dpad] f32 rows, zero-padded past dim. */
+inline const float* stage_padded_queries(MoannDevBuf& buf, const float* src,
+                                         bool src_on_device, uint64_t nq,
+                                         uint32_t dim, uint32_t dpad,
+                                         hipStream_t s) {
+    buf.ensure((size_t)nq * dpad * 4);
+    if (dim != dpad)
+        MOANN_HIP_CHECK(hipMemsetAsync(buf.ptr, 0, (size_t)nq * dpad * 4, s));
+    MOANN_HIP_CHECK(hipMemcpy2DAsync(
+        buf.ptr, (size_t)dpad * 4, src, (size_t)dim * 4, (size_t)dim * 4, nq,
+        src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    return buf.as<float>();
+}
+
+/* Bump-allocate a host job table's SoA arrays (8-byte aligned) in `buf` and
+ * enqueue their H2D copies on `stream`. `h` must stay untouched until those
+ * copies have run. An empty slot_base (rank scan) uploads as null. */
+inline ScanJobs upload_scan_jobs(const HostScanJobs& h, MoannDevBuf& buf,
+                                 hipStream_t stream) {
+    auto al8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+    const size_t nj = (size_t)h.njobs, ns = (size_t)h.nqslots;
+    buf.ensure(2 * al8(nj * 8) + 5 * al8(nj * 4) + al8(ns * 4) +
+               al8(ns * 8) + 64);
+    uint8_t* p = buf.as<uint8_t>();
+    auto up = [&](const auto& v) {
+        using T = typename std::decay_t<decltype(v)>::value_type;
+        const size_t bytes = v.size() * sizeof(T);
+        if (!bytes) return (const T*)nullptr;
+        MOANN_HIP_CHECK(hipMemcpyAsync(p, v.data(), bytes,
+                                       hipMemcpyHostToDevice, stream));
+        const T* r = (const T*)p;
+        p += al8(bytes);
+        return r;
+    };
+    /* ScanJobs member order (and the copy order the libraries always used) */
+    return ScanJobs {up(h.databaseg), up(h.gstart), up(h.gcount), up(h.rows),
+                     up(h.nq), up(h.qbase), up(h.qslot_query),
+                     up(h.qslot_outbase), up(h.slot_base), h.njobs};
+}
 
 }  // namespace moann
 

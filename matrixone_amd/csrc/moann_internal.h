@@ -7,15 +7,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-namespace moann {
+#include "moann_scan_plan.h" /* MetricKind, ScanVariant */
 
-/* Internal metric codes (template selectors for the scan kernel). */
-enum MetricKind : int {
-    KM_L2SQ = 0,  /* sum((x-q)^2)                     */
-    KM_IP = 1,    /* -x.q (MO convention)             */
-    KM_COS = 2,   /* 1 - x.q/(|x||q|), clamp, 0 -> 1  */
-    KM_L1 = 3,    /* sum|x-q|                         */
-};
+namespace moann {
 
 /* One scan job: a (list segment, query tile) pair. SoA device arrays. */
 struct ScanJobs {
@@ -37,15 +31,19 @@ struct ScanJobs {
  * i.e. [g][dpad/4][64][4] floats; row (g*64+l) holds vector dims 4*j4+c.
  * queries: [nq_total][dpad] device, zero-padded.
  * qnorms: [nq_total] sum-of-squares (cos only, else nullptr).
- * dists_out: ragged candidate buffer, written at qslot_outbase + row. */
-void launch_scan(int metric, int qt, const float* packed, const float* queries,
-                 const float* qnorms, int dpad, const ScanJobs& jobs,
-                 float* dists_out, hipStream_t stream,
+ * dists_out: ragged candidate buffer, written at qslot_outbase + row.
+ *
+ * The three scan launchers take the ScanVariant the job table was planned
+ * with (pick_scan) and switch on it, never re-deriving a kernel or width; a
+ * variant without a kernel throws std::logic_error before any HIP call. */
+void launch_scan(int metric, ScanVariant variant, const float* packed,
+                 const float* queries, const float* qnorms, int dpad,
+                 const ScanJobs& jobs, float* dists_out, hipStream_t stream,
                  const uint32_t* filter_bitset = nullptr);
 
 /* Hand-scheduled asm specialization of the scan for the flagship shape
  * (scan_asm768.hip): METRIC=L2SQ, dpad=768, QT=16, one group per wave.
- * launch_scan dispatches here itself when qt==16 fits; exposed for tests. */
+ * launch_scan dispatches here for ScanKind::F32_ASM768. */
 void launch_scan_asm768(const float* packed, const float* queries,
                         int dpad, const ScanJobs& jobs, float* dists_out,
                         hipStream_t stream,
@@ -99,11 +97,11 @@ bool launch_rank_gemm(int metric, const float* queries, const float* cents,
                       int nlist, int dpad, float* out, hipStream_t stream);
 
 /* Quantized (int8/uint8) list scan + helpers. */
-void launch_scan_i8(int metric, bool uns, const uint8_t* packed,
-                    const uint8_t* queries_q, const int32_t* qnorms,
-                    const int32_t* rownorms, int dpad,
+void launch_scan_i8(int metric, ScanVariant variant, bool uns,
+                    const uint8_t* packed, const uint8_t* queries_q,
+                    const int32_t* qnorms, const int32_t* rownorms, int dpad,
                     const ScanJobs& jb, float* dists_out, hipStream_t stream,
-                    const uint32_t* filter_bitset = nullptr, int qt = 8);
+                    const uint32_t* filter_bitset = nullptr);
 /* per-(group,lane) sum-of-squares over the packed byte rows (build-time,
  * feeds the dot-form scan's rn + qn - 2*dot L2) */
 void launch_bytes_pack16(const uint8_t* rows_q, int dpad,
@@ -141,9 +139,10 @@ void launch_quantize_half_rows(bool bf, const float* in, int64_t nrows,
                                uint16_t* out, hipStream_t stream);
 void launch_qnorms_h(bool bf, const uint16_t* q, int nq, int dpad,
                      float* out, hipStream_t stream);
-void launch_scan_h(int metric, bool bf, const uint16_t* packed,
-                   const uint16_t* queries_h, const float* qnorms, int dpad,
-                   const ScanJobs& jb, float* dists_out, hipStream_t stream,
+void launch_scan_h(int metric, ScanVariant variant, bool bf,
+                   const uint16_t* packed, const uint16_t* queries_h,
+                   const float* qnorms, int dpad, const ScanJobs& jb,
+                   float* dists_out, hipStream_t stream,
                    const uint32_t* filter_bitset = nullptr);
 void launch_qnorms_i8(bool uns, const uint8_t* q, int nq, int dpad,
                       int32_t* out, hipStream_t stream);

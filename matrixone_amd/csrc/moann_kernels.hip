@@ -24,6 +24,8 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <stdexcept>
+#include <string>
 
 #include "moann_internal.h"
 
@@ -291,6 +293,14 @@ __global__ __launch_bounds__(256) void scan_kernel(
     }
 }
 
+/* planner/launcher disagreement (the bug class that leaves tile lanes
+ * unscanned): reported by name, before anything is enqueued */
+[[noreturn]] static void bad_variant(const char* launcher, ScanVariant v) {
+    throw std::logic_error(std::string(launcher) + ": no kernel for scan " +
+                           scan_kind_name(v.kind) + " qt=" +
+                           std::to_string(v.qt));
+}
+
 template <int METRIC>
 static void launch_scan_qt(int qt, const float* packed, const float* queries,
                            const float* qnorms, int dpad, const ScanJobs& jb,
@@ -300,15 +310,7 @@ static void launch_scan_qt(int qt, const float* packed, const float* queries,
 #define ARGS packed, queries, qnorms, dpad, jb.databaseg, jb.gstart, \
     jb.gcount, jb.rows, jb.nq, jb.qbase, jb.qslot_query, jb.qslot_outbase, \
     jb.slot_base, filter_bitset, dists_out
-    switch (qt) {
-    case 16:
-        hipLaunchKernelGGL((scan_kernel<METRIC, 16, 1>), grid, block,
-                           (16 * dpad + 16) * sizeof(float), stream, ARGS);
-        break;
-    case 12:
-        hipLaunchKernelGGL((scan_kernel<METRIC, 12, 2>), grid, block,
-                           (12 * dpad + 12) * sizeof(float), stream, ARGS);
-        break;
+    switch (qt) { /* launch_scan admits only these four widths */
     case 8:
         hipLaunchKernelGGL((scan_kernel<METRIC, 8, 2>), grid, block,
                            (8 * dpad + 8) * sizeof(float), stream, ARGS);
@@ -329,23 +331,21 @@ static void launch_scan_qt(int qt, const float* packed, const float* queries,
 #undef ARGS
 }
 
-void launch_scan(int metric, int qt, const float* packed, const float* queries,
-                 const float* qnorms, int dpad, const ScanJobs& jb,
-                 float* dists_out, hipStream_t stream,
+void launch_scan(int metric, ScanVariant v, const float* packed,
+                 const float* queries, const float* qnorms, int dpad,
+                 const ScanJobs& jb, float* dists_out, hipStream_t stream,
                  const uint32_t* filter_bitset) {
+    const int qt = v.qt;
+    const bool asm768 = v.kind == ScanKind::F32_ASM768 && qt == 16 &&
+                        metric == KM_L2SQ && dpad == 768;
+    const bool generic = v.kind == ScanKind::F32 &&
+                         (qt == 8 || qt == 4 || qt == 2 || qt == 1);
+    if (!asm768 && !generic) bad_variant("launch_scan", v);
     if (jb.njobs == 0) return;
-    /* flagship shape -> hand-scheduled asm kernel (scan_asm768.hip);
-     * MOANN_SCAN=generic forces the compiler-scheduled path for A/B */
-    if (metric == KM_L2SQ && qt == 16 && dpad == 768) {
-        static const bool generic = [] {
-            const char* e = getenv("MOANN_SCAN");
-            return e && strcmp(e, "generic") == 0;
-        }();
-        if (!generic) {
-            launch_scan_asm768(packed, queries, dpad, jb, dists_out, stream,
-                               filter_bitset);
-            return;
-        }
+    if (asm768) { /* flagship shape: hand-scheduled kernel (scan_asm768.hip) */
+        launch_scan_asm768(packed, queries, dpad, jb, dists_out, stream,
+                           filter_bitset);
+        return;
     }
     switch (metric) {
     case KM_L2SQ: launch_scan_qt<KM_L2SQ>(qt, packed, queries, qnorms, dpad, jb, dists_out, stream, filter_bitset); break;
@@ -1025,10 +1025,12 @@ static void launch_scan_h_m(bool bf, const uint16_t* packed,
 #undef HFARGS
 }
 
-void launch_scan_h(int metric, bool bf, const uint16_t* packed,
-                   const uint16_t* queries_h, const float* qnorms, int dpad,
-                   const ScanJobs& jb, float* dists_out, hipStream_t stream,
+void launch_scan_h(int metric, ScanVariant v, bool bf,
+                   const uint16_t* packed, const uint16_t* queries_h,
+                   const float* qnorms, int dpad, const ScanJobs& jb,
+                   float* dists_out, hipStream_t stream,
                    const uint32_t* filter_bitset) {
+    if (v.kind != ScanKind::HALF || v.qt != 8) bad_variant("launch_scan_h", v);
     if (!jb.njobs) return;
     switch (metric) {
     case KM_L2SQ: launch_scan_h_m<KM_L2SQ>(bf, packed, queries_h, qnorms, dpad, jb, dists_out, stream, filter_bitset); break;
@@ -1600,13 +1602,12 @@ static void launch_scan_i8_m(bool uns, const uint8_t* packed,
                              const int32_t* rownorms, int dpad,
                              const ScanJobs& jb, float* dists_out,
                              hipStream_t stream,
-                             const uint32_t* filter_bitset, int qt) {
+                             const uint32_t* filter_bitset, ScanVariant v) {
     const dim3 grid(jb.njobs), block(256);
+    const int qt = v.qt;
     const size_t shmem = (size_t)qt * dpad + (size_t)qt * 4 + 16;
-    /* dot-form kernel needs 16-dim-aligned rows and the precomputed row
-     * norms; falls back to the uchar4 kernel otherwise (odd dims).
-     * qt MUST match the job builder's tile width (the r01 refine bug). */
-    const bool dot = (dpad & 15) == 0 && rownorms != nullptr;
+    /* dot form (16-dim-aligned rows + row norms) or the uchar4 kernel */
+    const bool dot = v.kind == ScanKind::BYTE_DOT;
 #define I8ARGS packed, queries_q, qnorms, dpad, jb.databaseg, jb.gstart, \
     jb.gcount, jb.rows, jb.nq, jb.qbase, jb.qslot_query, jb.qslot_outbase, \
     jb.slot_base, filter_bitset, dists_out
@@ -1620,19 +1621,13 @@ static void launch_scan_i8_m(bool uns, const uint8_t* packed,
         else
             hipLaunchKernelGGL((scan_i8_dot_kernel<METRIC, false, 16>), grid,
                                block, shmem, stream, I8DARGS);
-    } else if (dot && qt == 8) {
+    } else if (dot) {
         if (uns)
             hipLaunchKernelGGL((scan_i8_dot_kernel<METRIC, true, 8>), grid,
                                block, shmem, stream, I8DARGS);
         else
             hipLaunchKernelGGL((scan_i8_dot_kernel<METRIC, false, 8>), grid,
                                block, shmem, stream, I8DARGS);
-    } else if (qt != 8) {
-        /* no QT!=8 instantiation of the uchar4 kernel: loud geometry error
-         * instead of silently unscanned tile lanes */
-        (void)hipErrorInvalidValue;
-        hipLaunchKernelGGL((scan_i8_kernel<METRIC, true>), dim3(0), block,
-                           shmem, stream, I8ARGS); /* grid 0 -> launch err */
     } else if (uns)
         hipLaunchKernelGGL((scan_i8_kernel<METRIC, true>), grid, block, shmem,
                            stream, I8ARGS);
@@ -1643,17 +1638,24 @@ static void launch_scan_i8_m(bool uns, const uint8_t* packed,
 #undef I8DARGS
 }
 
-void launch_scan_i8(int metric, bool uns, const uint8_t* packed,
-                    const uint8_t* queries_q, const int32_t* qnorms,
-                    const int32_t* rownorms, int dpad,
+void launch_scan_i8(int metric, ScanVariant v, bool uns,
+                    const uint8_t* packed, const uint8_t* queries_q,
+                    const int32_t* qnorms, const int32_t* rownorms, int dpad,
                     const ScanJobs& jb, float* dists_out, hipStream_t stream,
-                    const uint32_t* filter_bitset, int qt) {
+                    const uint32_t* filter_bitset) {
+    /* the byte kernels' only tile widths: dot form 16 and 8, uchar4 form 8 */
+    const bool dot_ok = v.kind == ScanKind::BYTE_DOT &&
+                        (v.qt == 16 || v.qt == 8);
+    const bool u4_ok = v.kind == ScanKind::BYTE_U4 && v.qt == 8;
+    if (!dot_ok && !u4_ok) bad_variant("launch_scan_i8", v);
+    if (dot_ok && !rownorms)
+        throw std::logic_error("launch_scan_i8: BYTE_DOT without row norms");
     if (!jb.njobs) return;
     switch (metric) {
-    case KM_L2SQ: launch_scan_i8_m<KM_L2SQ>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, qt); break;
-    case KM_IP:   launch_scan_i8_m<KM_IP>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, qt); break;
-    case KM_COS:  launch_scan_i8_m<KM_COS>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, qt); break;
-    default:      launch_scan_i8_m<KM_L1>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, qt); break;
+    case KM_L2SQ: launch_scan_i8_m<KM_L2SQ>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, v); break;
+    case KM_IP:   launch_scan_i8_m<KM_IP>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, v); break;
+    case KM_COS:  launch_scan_i8_m<KM_COS>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, v); break;
+    default:      launch_scan_i8_m<KM_L1>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, v); break;
     }
 }
 

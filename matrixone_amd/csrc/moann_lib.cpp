@@ -33,65 +33,16 @@
 
 #include "../../include/moann.h"
 #include "moann_host_common.h"
-#include "moann_internal.h"
 
 namespace {
 
 using namespace moann;
 
-#define HIP_CHECK(expr)                                                     \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess)                                               \
-            throw std::runtime_error(std::string("HIP error: ") +           \
-                                     hipGetErrorString(_e) + " at " #expr); \
-    } while (0)
-
-#define KCHECK(tag)                                                          \
-    do {                                                                     \
-        hipError_t _e = hipGetLastError();                                   \
-        if (_e != hipSuccess)                                                \
-            throw std::runtime_error(std::string("HIP launch error [") +     \
-                                     tag + "]: " + hipGetErrorString(_e));   \
-    } while (0)
-
-/* errmsg convention: cgo/cuvs/helper.h:59 — errmsg is a char** as void*. */
-void set_errmsg(void* errmsg, const char* context, const char* message) {
-    if (!errmsg) return;
-    std::string full = std::string(context) + ": " + message;
-    *(char**)errmsg = strdup(full.c_str());
-}
-
-int metric_kind(distance_type_t m) {
-    switch (m) {
-    case DistanceType_L2Expanded:
-    case DistanceType_L2SqrtExpanded: return KM_L2SQ;
-    case DistanceType_CosineExpanded: return KM_COS;
-    case DistanceType_InnerProduct: return KM_IP;
-    case DistanceType_L1: return KM_L1;
-    default: throw std::runtime_error("unsupported metric");
-    }
-}
-
-/* grow-only device buffer (the q_dev_buf/neighbors_buf shape of
- * cgo/cuvs/cuvs_worker.hpp:50-150, minus RMM) */
-struct DevBuf {
-    void* ptr = nullptr;
-    size_t bytes = 0;
-    void ensure(size_t need) {
-        if (need <= bytes) return;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-        HIP_CHECK(hipMalloc(&ptr, need));
-        bytes = need;
-    }
-    ~DevBuf() {
-        if (ptr) (void)hipFree(ptr);
-    }
-    template <typename T>
-    T* as() { return (T*)ptr; }
-};
+/* local short names for the shared helpers (moann_host_common.h) */
+#define HIP_CHECK MOANN_HIP_CHECK
+#define KCHECK MOANN_KCHECK
+using DevBuf = MoannDevBuf;
+constexpr auto set_errmsg = moann_set_errmsg;
 
 using Result = MoannResult;  /* shared with the PQ/HNSW libs so the
     gpu_ivf_flat_get_* readout works on every family's results */
@@ -130,6 +81,20 @@ struct SearchCtx {
     size_t h_out_bytes = 0;
     std::vector<uint32_t> h_filter; /* staged filter words: must outlive the
         async H2D when the submit path returns before the copy runs */
+    /* host side of the scan plan, reused across searches (same lifetime
+     * rule: their async H2D copies complete before this ctx is reused) */
+    std::vector<int32_t> h_probe; /* [nq][probe] probed lists, rank order */
+    HostScanJobs rank_jobs;
+    ProbeOffsets offs;
+    ListScanPlan lists;
+    struct Call { /* the search in flight through the stages below */
+        uint64_t nq = 0;
+        uint32_t limit = 0, probe = 0;
+        ScanChoice scan {};
+        bool refine = false;            /* two-stage scan active            */
+        const float* d_q = nullptr;     /* [nq][dpad] padded queries        */
+        const float* d_qn = nullptr;    /* [nq] |q|^2, when a stage needs it */
+    } call;
     MoannResult* pending = nullptr; /* submitted, not yet collected */
     void* parent = nullptr;         /* IvfIndex*, for perf accumulation */
     void ensure(void* ix) {
@@ -283,42 +248,6 @@ struct IvfIndex {
     }
 };
 
-int pick_qt(int kmetric, uint32_t dpad, bool narrow) {
-    /* MOANN_QT overrides for A/B tuning. QT=16 is honored only for the
-     * vetted flagship shape (L2SQ, dpad 768 — the asm kernel, or
-     * MOANN_SCAN=generic measured there in r01): the generic f32 QT16
-     * instantiation miscomputed at small dpad in the r02 byte-QT16
-     * triage (7 parity failures when the rank stage ran it at d=64/96),
-     * so other shapes clamp to 8 instead of silently going wrong. */
-    if (const char* e = getenv("MOANN_QT")) {
-        const int v = atoi(e);
-        if (v == 16) {
-            if (kmetric == KM_L2SQ && dpad == 768) return 16;
-        } else if (v == 1 || v == 2 || v == 4 || v == 8 || v == 12) {
-            return v;
-        }
-    }
-    /* flagship f32 shape: the hand-scheduled QT=16 asm kernel
-     * (scan_asm768.hip) — lowest tile re-read multiplicity AND a pipelined
-     * load ring. MOANN_SCAN=generic drops back to the QT=8 policy below. */
-    if (!narrow && kmetric == KM_L2SQ && dpad == 768) {
-        const char* e = getenv("MOANN_SCAN");
-        if (!(e && strcmp(e, "generic") == 0)) return 16;
-    }
-    /* QT query rows in LDS; <= 52 KiB keeps >=3 blocks/CU resident.
-     * QT=16 halves list re-reads when many queries probe one list (the
-     * hub-list multiplicity); VALU ceiling at QT=16/d768 is ~9.8 TB/s,
-     * still above the HBM bound. */
-    /* QT=8 measured best end-to-end: hipcc pipelines its inner loop with
-     * counted vmcnt (4 loads in flight) where the QT=16 instantiation
-     * degrades to a full vmcnt(0) stall per iteration; the extra tile
-     * re-reads at QT=8 mostly hit the XCD-affine L2 (physical fetch ~1.4x
-     * compulsory vs 1.14x at QT=16, but 4.6 vs 2.6 TB/s sustained). */
-    for (int qt : {8, 4, 2, 1})
-        if ((size_t)qt * dpad * 4 + qt * 4 <= 52 * 1024) return qt;
-    return 1;
-}
-
 /* Build the interleaved layout for an arbitrary row set (used for both the
  * entry lists and the centroid matrix-as-one-list). */
 void pack_lists(IvfIndex* ix, const float* d_rows, int64_t nrows,
@@ -465,6 +394,244 @@ std::vector<float> base_to_f32(quantization_t btype, const void* src,
 
 double collect_result(MoannResult* res); /* below; returns kernel-window ms */
 
+/* The A/B tuning environment of the scan path, read once per process: the
+ * only getenv on it (MOANN_RANK is read where the build picks the rank). */
+const ScanOverrides& scan_overrides() {
+    static const ScanOverrides ov = [] {
+        const char *sc = getenv("MOANN_SCAN"), *bq = getenv("MOANN_BYTE_QT"),
+                   *cg = getenv("MOANN_CHUNKG");
+        ScanOverrides o;
+        o.generic_f32 = sc && strcmp(sc, "generic") == 0;
+        o.byte_qt8 = bq && atoi(bq) == 8;
+        o.chunk_g = cg ? atoi(cg) : 0;
+        return o;
+    }();
+    return ov;
+}
+
+/* run_search is the stages below in order, all enqueued on cx->stream; the
+ * per-call state they share is cx->call.
+ * 1. queries to device, padded to dpad (+ |q|^2 where a stage needs it) */
+void stage_queries(IvfIndex* ix, SearchCtx* cx, const float* queries,
+                   bool queries_on_device) {
+    SearchCtx::Call& c = cx->call;
+    const int dpad = (int)ix->dpad;
+    const hipStream_t s = cx->stream;
+    c.d_q = stage_padded_queries(cx->w_queries, queries, queries_on_device,
+                                 c.nq, ix->dim, ix->dpad, s);
+    c.d_qn = nullptr;
+    const bool use_mfma_rank = ix->rank_mfma && ix->kmetric != KM_L1;
+    if (ix->kmetric == KM_COS || use_mfma_rank) {
+        cx->w_qnorms.ensure(c.nq * 4);
+        launch_qnorms(c.d_q, (int)c.nq, dpad, cx->w_qnorms.as<float>(), s);
+        KCHECK("qnorms");
+        c.d_qn = cx->w_qnorms.as<float>();
+    }
+}
+
+/* 2. centroid rank: scan the centroid matrix as one "list" of nlist rows (or
+ * the MFMA GEMM), then top-probe per query (search.go:265-308 rankCentroids) */
+void rank_centroids(IvfIndex* ix, SearchCtx* cx) {
+    const SearchCtx::Call& c = cx->call;
+    const int dpad = (int)ix->dpad, nq = (int)c.nq;
+    const hipStream_t s = cx->stream;
+    cx->w_cdists.ensure((size_t)c.nq * ix->nlist * 4);
+    if (ix->rank_mfma && ix->kmetric != KM_L1) {
+        HIP_CHECK(hipEventRecord(cx->ev[0], s));
+        launch_rank_gemm(ix->kmetric, c.d_q, ix->d_cent_rows, c.d_qn,
+                         ix->d_cnorms, nq, (int)ix->nlist, dpad,
+                         cx->w_cdists.as<float>(), s);
+        KCHECK("rank-gemm");
+    } else {
+        plan_rank_scan(c.nq, c.scan.rank.qt, ix->nlist, ix->cent_groups,
+                       cx->rank_jobs);
+        const ScanJobs jb = upload_scan_jobs(cx->rank_jobs, cx->w_jobs, s);
+        HIP_CHECK(hipEventRecord(cx->ev[0], s));
+        launch_scan(ix->kmetric, c.scan.rank, ix->d_cent_packed, c.d_q,
+                    c.d_qn, dpad, jb, cx->w_cdists.as<float>(), s);
+        KCHECK("rank-scan");
+    }
+    HIP_CHECK(hipEventRecord(cx->ev[1], s));
+    cx->w_csel_slots.ensure((size_t)c.nq * c.probe * 4);
+    cx->w_csel_dists.ensure((size_t)c.nq * c.probe * 4);
+    launch_topk(cx->w_cdists.as<float>(), nullptr, ix->nlist, nq,
+                (int)c.probe, cx->w_csel_slots.as<int32_t>(),
+                cx->w_csel_dists.as<float>(), s);
+    KCHECK("rank-topk");
+}
+
+/* 3. D2H the probe selection — the pipeline's one host sync — and plan the
+ * list scan (findCentroids -> scanEntries shape, search.go:917-1005) */
+void fetch_probe_and_plan(IvfIndex* ix, SearchCtx* cx) {
+    const SearchCtx::Call& c = cx->call;
+    const hipStream_t s = cx->stream;
+    cx->h_probe.resize((size_t)c.nq * c.probe);
+    HIP_CHECK(hipMemcpyAsync(cx->h_probe.data(), cx->w_csel_slots.ptr,
+                             cx->h_probe.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipGetLastError());
+    plan_probe_offsets(cx->h_probe.data(), c.nq, c.probe, ix->list_rows,
+                       cx->offs);
+    plan_list_scan(cx->h_probe.data(), c.nq, c.probe, c.scan.list.qt,
+                   list_chunk_groups(ix->qtype, scan_overrides()),
+                   ix->list_rows, ix->list_gbase, ix->list_slot_base,
+                   cx->offs, cx->lists);
+}
+
+/* 4. list scan into the ragged candidate buffer: prepare the queries the
+ * way the variant's kernel reads them, then one launch. */
+void scan_lists(IvfIndex* ix, SearchCtx* cx, const uint32_t* filter_words) {
+    const SearchCtx::Call& c = cx->call;
+    const int dpad = (int)ix->dpad, nq = (int)c.nq;
+    const hipStream_t s = cx->stream;
+    const ScanVariant v = c.scan.list;
+    const uint32_t* d_filter = nullptr;
+    if (filter_words) {
+        const size_t fw = (size_t)((ix->count + 31) / 32);
+        cx->h_filter.assign(filter_words, filter_words + fw);
+        cx->w_filter.ensure(fw * 4);
+        HIP_CHECK(hipMemcpyAsync(cx->w_filter.ptr, cx->h_filter.data(),
+                                 fw * 4, hipMemcpyHostToDevice, s));
+        d_filter = cx->w_filter.as<uint32_t>();
+    }
+    cx->w_cand.ensure(std::max<int64_t>(1, cx->offs.total_cand) * 4);
+    float* d_cand = cx->w_cand.as<float>();
+    const ScanJobs jb = upload_scan_jobs(cx->lists.jobs, cx->w_qslots, s);
+    HIP_CHECK(hipEventRecord(cx->ev[2], s));
+    switch (v.kind) {
+    case ScanKind::BYTE_DOT:
+    case ScanKind::BYTE_U4: {
+        /* the byte image — the internal clip-quantized one for the refine
+         * first pass, else the int8/uint8 storage — and the map that narrows
+         * the queries like its entries (quantizer.go ApplyInt8/entry SQL) */
+        const bool uns = !c.refine && ix->qtype == Quantization_UINT8;
+        const uint8_t* image = c.refine ? ix->d_packed_rq : ix->d_packed_q;
+        const int32_t* rownorms =
+            c.refine ? ix->d_rownorm_rq : ix->d_rownorm_q;
+        const double mul = c.refine ? ix->rq_mul : ix->quant_mul;
+        const double add = c.refine ? ix->rq_add : ix->quant_add;
+        cx->w_queries_q.ensure((size_t)c.nq * dpad);
+        uint8_t* d_qq = cx->w_queries_q.as<uint8_t>();
+        launch_quantize_rows(uns, c.d_q, (int64_t)c.nq, dpad, (int)ix->dim,
+                             dpad, (float)mul, (float)add, d_qq, s);
+        KCHECK("query-quantize");
+        const int32_t* d_qni = nullptr;
+        if (ix->kmetric == KM_COS || ix->kmetric == KM_L2SQ) {
+            /* cos denominators; also qn of the dot-form L2 */
+            cx->w_qnorms_i.ensure(c.nq * 4);
+            launch_qnorms_i8(uns, d_qq, nq, dpad,
+                             cx->w_qnorms_i.as<int32_t>(), s);
+            d_qni = cx->w_qnorms_i.as<int32_t>();
+        }
+        launch_scan_i8(ix->kmetric, v, uns, image, d_qq, d_qni, rownorms,
+                       dpad, jb, d_cand, s, d_filter);
+        break;
+    }
+    case ScanKind::HALF: {
+        /* plain-cast narrow search: query cast RTNE like the entries
+         * (relation_search.go:56-63), decoded-f32 distance */
+        const bool bf = ix->qtype == Quantization_BF16;
+        cx->w_queries_q.ensure((size_t)c.nq * dpad * 2);
+        uint16_t* d_qh = cx->w_queries_q.as<uint16_t>();
+        launch_quantize_half_rows(bf, c.d_q, (int64_t)c.nq, dpad,
+                                  (int)ix->dim, dpad, d_qh, s);
+        KCHECK("query-half-cast");
+        const float* d_qnh = nullptr;
+        if (ix->kmetric == KM_COS) {
+            cx->w_qnorms_i.ensure(c.nq * 4);
+            launch_qnorms_h(bf, d_qh, nq, dpad, cx->w_qnorms_i.as<float>(),
+                            s);
+            d_qnh = cx->w_qnorms_i.as<float>();
+        }
+        launch_scan_h(ix->kmetric, v, bf, (const uint16_t*)ix->d_packed_q,
+                      d_qh, d_qnh, dpad, jb, d_cand, s, d_filter);
+        break;
+    }
+    case ScanKind::F32:
+    case ScanKind::F32_ASM768:
+        launch_scan(ix->kmetric, v, ix->d_packed, c.d_q, c.d_qn, dpad, jb,
+                    d_cand, s, d_filter);
+        break;
+    }
+    KCHECK("list-scan");
+    HIP_CHECK(hipEventRecord(cx->ev[3], s));
+}
+
+/* 5. per-query top-limit over the candidates; for the two-stage scan: top-R
+ * by byte distance -> exact f32 re-rank -> top-limit -> candidate slots */
+void select_candidates(IvfIndex* ix, SearchCtx* cx) {
+    const SearchCtx::Call& c = cx->call;
+    const int dpad = (int)ix->dpad, nq = (int)c.nq, limit = (int)c.limit;
+    const hipStream_t s = cx->stream;
+    upload_vector(cx->w_qoffs, cx->offs.qoffs, s);
+    upload_vector(cx->w_probe_lists, cx->h_probe, s);
+    upload_vector(cx->w_probe_offs, cx->offs.probe_offs, s);
+    cx->w_sel_slots.ensure((size_t)c.nq * limit * 4);
+    cx->w_sel_dists.ensure((size_t)c.nq * limit * 4);
+    HIP_CHECK(hipEventRecord(cx->ev[4], s));
+    if (c.refine) {
+        const int R = std::max<int>(limit, ix->refine_depth);
+        cx->w_rsel_slots.ensure((size_t)c.nq * R * 4);
+        cx->w_rsel_dists.ensure((size_t)c.nq * R * 4);
+        launch_topk(cx->w_cand.as<float>(), cx->w_qoffs.as<int64_t>(), 0, nq,
+                    R, cx->w_rsel_slots.as<int32_t>(),
+                    cx->w_rsel_dists.as<float>(), s);
+        KCHECK("refine-topR");
+        cx->w_refined.ensure((size_t)c.nq * R * 4);
+        launch_refine(ix->kmetric, ix->d_rows_f32, c.d_q, c.d_qn,
+                      (int)ix->dim, dpad, R, nq,
+                      cx->w_rsel_slots.as<int32_t>(),
+                      cx->w_rsel_dists.as<float>(),
+                      cx->w_probe_lists.as<int32_t>(),
+                      cx->w_probe_offs.as<int64_t>(), ix->d_list_slot_base,
+                      (int)c.probe, cx->w_refined.as<float>(), s);
+        KCHECK("refine");
+        cx->w_sel2.ensure((size_t)c.nq * limit * 4);
+        launch_topk(cx->w_refined.as<float>(), nullptr, R, nq, limit,
+                    cx->w_sel2.as<int32_t>(), cx->w_sel_dists.as<float>(), s);
+        KCHECK("refine-topk");
+        launch_compose_select(cx->w_sel2.as<int32_t>(),
+                              cx->w_rsel_slots.as<int32_t>(), R, limit, nq,
+                              cx->w_sel_slots.as<int32_t>(), s);
+        KCHECK("refine-compose");
+    } else {
+        launch_topk(cx->w_cand.as<float>(), cx->w_qoffs.as<int64_t>(), 0, nq,
+                    limit, cx->w_sel_slots.as<int32_t>(),
+                    cx->w_sel_dists.as<float>(), s);
+        KCHECK("cand-topk");
+    }
+    HIP_CHECK(hipEventRecord(cx->ev[5], s));
+}
+
+/* 6. id gather + score transform, then D2H through the ctx's pinned bounce
+ * (pageable-async degrades to a host-blocking copy on ROCm, which would
+ * serialize the pipeline) */
+void gather_results(IvfIndex* ix, SearchCtx* cx) {
+    const SearchCtx::Call& c = cx->call;
+    const size_t n = (size_t)c.nq * c.limit;
+    const hipStream_t s = cx->stream;
+    const int do_sqrt = ix->metric == DistanceType_L2SqrtExpanded;
+    const double inv_mul2 =
+        (ix->quant_mul != 0.0 && ix->quant_mul != 1.0)
+            ? 1.0 / (ix->quant_mul * ix->quant_mul) : 1.0;
+    cx->w_out_ids.ensure(n * 8);
+    cx->w_out_dists.ensure(n * 4);
+    launch_gather(cx->w_sel_slots.as<int32_t>(), cx->w_sel_dists.as<float>(),
+                  cx->w_probe_lists.as<int32_t>(),
+                  cx->w_probe_offs.as<int64_t>(), ix->d_list_slot_base,
+                  ix->d_id_by_slot, (int)c.probe, (int)c.nq, (int)c.limit,
+                  do_sqrt, inv_mul2, cx->w_out_ids.as<int64_t>(),
+                  cx->w_out_dists.as<float>(), s);
+    KCHECK("gather");
+    cx->ensure_hout(n * 12);
+    int64_t* ho_ids = (int64_t*)cx->h_out;
+    float* ho_dists = (float*)(ho_ids + n);
+    HIP_CHECK(hipMemcpyAsync(ho_ids, cx->w_out_ids.ptr, n * 8,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(ho_dists, cx->w_out_dists.ptr, n * 4,
+                             hipMemcpyDeviceToHost, s));
+}
+
 std::unique_ptr<Result> run_search(IvfIndex* ix, const float* queries,
                                    bool queries_on_device, uint64_t nq,
                                    uint32_t limit, uint32_t n_probes,
@@ -482,472 +649,53 @@ std::unique_ptr<Result> run_search(IvfIndex* ix, const float* queries,
     if (!ix->built) throw std::runtime_error("index not built");
     if (ix->count == 0) return res;
     if (limit > 4096) throw std::runtime_error("limit > 4096 unsupported");
-
-    uint32_t probe = std::min<uint32_t>(n_probes ? n_probes : 1, ix->nlist);
+    const uint32_t probe =
+        std::min<uint32_t>(n_probes ? n_probes : 1, ix->nlist);
     if (probe > 4096) throw std::runtime_error("n_probes > 4096 unsupported");
-    const int dpad = (int)ix->dpad;
-    const hipStream_t s = cx->stream;
     ix->perf.ensure();
-    const int do_sqrt = ix->metric == DistanceType_L2SqrtExpanded;
-    const double inv_mul2 =
-        (ix->quant_mul != 0.0 && ix->quant_mul != 1.0)
-            ? 1.0 / (ix->quant_mul * ix->quant_mul) : 1.0;
+
+    SearchCtx::Call& c = cx->call;
+    c.nq = nq;
+    c.limit = limit;
+    c.probe = probe;
+    c.refine = ix->qtype == Quantization_F32 && ix->refine_depth > 0 &&
+               ix->d_packed_rq != nullptr;
+    /* the one scan decision: job tables are planned at, and launchers
+     * switch on, these variants (moann_scan_plan.h) */
+    c.scan = pick_scan(ix->kmetric, (int)ix->dpad, ix->qtype, c.refine,
+                       (c.refine ? ix->d_rownorm_rq : ix->d_rownorm_q) !=
+                           nullptr,
+                       scan_overrides());
 
     const auto t_all0 = std::chrono::steady_clock::now();
-    /* 1. queries to device, padded to dpad */
-    cx->w_queries.ensure((size_t)nq * dpad * 4);
-    if ((int)ix->dim != dpad)
-        HIP_CHECK(hipMemsetAsync(cx->w_queries.ptr, 0, (size_t)nq * dpad * 4, s));
-    HIP_CHECK(hipMemcpy2DAsync(cx->w_queries.ptr, (size_t)dpad * 4, queries,
-                               (size_t)ix->dim * 4, (size_t)ix->dim * 4, nq,
-                               queries_on_device ? hipMemcpyDeviceToDevice
-                                                 : hipMemcpyHostToDevice, s));
-    const float* d_q = cx->w_queries.as<float>();
-    const float* d_qn = nullptr;
-    const bool use_mfma_rank = ix->rank_mfma && ix->kmetric != KM_L1;
-    if (ix->kmetric == KM_COS || use_mfma_rank) {
-        cx->w_qnorms.ensure(nq * 4);
-        launch_qnorms(d_q, (int)nq, dpad, cx->w_qnorms.as<float>(), s);
-        KCHECK("qnorms");
-        d_qn = cx->w_qnorms.as<float>();
-    }
-
-    /* 2. centroid rank: scan the centroid matrix (one "list" of nlist rows),
-     * then top-probe per query (ivfflat/search.go:265-308 rankCentroids). */
-    /* The job tile width MUST match the kernel that scans the lists: the
-     * byte kernels (int8/uint8 storage AND the refine byte first pass) and
-     * the half kernels are QT=8; only the f32 scan has the QT=16 asm
-     * specialization. Round-1 latent bug: refine jobs were built at the f32
-     * QT=16 while scan_i8_dot_kernel processes t<8 — tile lanes 8..15 were
-     * never scanned and their candidates kept stale buffer contents (masked
-     * in tests by same-query buffer aliasing; recall 0.9414 at 10M). */
-    const bool refine_scan = ix->qtype == Quantization_F32 &&
-                             ix->refine_depth > 0 &&
-                             ix->d_packed_rq != nullptr;
-    /* The byte DOT kernel also has a QT=16 instantiation — use the wide
-     * tile whenever the byte path will take the dot form (halves the
-     * query-tile re-read multiplicity, measured 1.14x compulsory at QT=8);
-     * the uchar4 fallback and the half kernels stay QT=8. */
-    const bool half_st = ix->qtype == Quantization_F16 ||
-                         ix->qtype == Quantization_BF16;
-    bool byte_dot16 = false;
-    if (refine_scan)
-        byte_dot16 = (ix->dpad & 15) == 0 && ix->d_rownorm_rq &&
-                     (size_t)16 * ix->dpad + 80 <= 48 * 1024;
-    else if (ix->qtype != Quantization_F32 && !half_st)
-        byte_dot16 = (ix->dpad & 15) == 0 && ix->d_rownorm_q &&
-                     (size_t)16 * ix->dpad + 80 <= 48 * 1024;
-    if (const char* e = getenv("MOANN_BYTE_QT"))
-        if (atoi(e) == 8) byte_dot16 = false; /* A/B override */
-    /* rank (f32 centroid scan) keeps its own tile width: only the flagship
-     * (L2SQ, 768) has a vetted QT=16 f32 path (the asm kernel); the byte
-     * list scan may still go wide independently */
-    const int qt_rank = pick_qt(ix->kmetric, ix->dpad,
-                                ix->qtype != Quantization_F32 ||
-                                    refine_scan);
-    /* The byte list scan has exactly two tile widths (dot-form 16, and 8 for
-     * both the dot-form and the uchar4 kernel). qt_rank is sized for F32
-     * query tiles in LDS and drops to 4 above dpad 1663 — a width no byte
-     * kernel has (launch_scan_i8 rejects it), while 8 byte rows of any
-     * supported dpad fit LDS with room to spare. */
-    const bool byte_scan = refine_scan ||
-                           (ix->qtype != Quantization_F32 && !half_st);
-    const int qt = byte_dot16 ? 16 : (byte_scan ? 8 : qt_rank);
-    if (use_mfma_rank) {
-        cx->w_cdists.ensure((size_t)nq * ix->nlist * 4);
-        HIP_CHECK(hipEventRecord(cx->ev[0], s));
-        launch_rank_gemm(ix->kmetric, d_q, ix->d_cent_rows, d_qn,
-                         ix->d_cnorms, (int)nq, (int)ix->nlist, dpad,
-                         cx->w_cdists.as<float>(), s);
-        KCHECK("rank-gemm");
-        HIP_CHECK(hipEventRecord(cx->ev[1], s));
-        cx->w_csel_slots.ensure((size_t)nq * probe * 4);
-        cx->w_csel_dists.ensure((size_t)nq * probe * 4);
-        launch_topk(cx->w_cdists.as<float>(), nullptr, ix->nlist, (int)nq,
-                    (int)probe, cx->w_csel_slots.as<int32_t>(),
-                    cx->w_csel_dists.as<float>(), s);
-        KCHECK("rank-topk");
-    } else {
-        cx->w_cdists.ensure((size_t)nq * ix->nlist * 4);
-        /* tile queries, chunk centroid groups to fill the chip */
-        const int qt = qt_rank; /* shadow: the rank stage's tile width */
-        const int ntiles = (int)((nq + qt - 1) / qt);
-        const int64_t cgroups = ix->cent_groups;
-        /* target ~1024 jobs: enough to fill 256 CUs without paying the
-         * 48 KiB query-tile LDS fill per tiny single-group job */
-        int64_t want_chunks = std::min<int64_t>(
-            cgroups, std::max<int64_t>(1, (1024 + ntiles - 1) / ntiles));
-        const int chunk = (int)((cgroups + want_chunks - 1) / want_chunks);
-        const int nchunk = (int)((cgroups + chunk - 1) / chunk);
-        const int njobs = ntiles * nchunk;
-        const int nqslots = ntiles * qt;
-        /* host staging layout */
-        std::vector<int64_t> databaseg(njobs), qslot_outbase(nqslots);
-        std::vector<int32_t> gstart(njobs), gcount(njobs), rows(njobs),
-            jnq(njobs), qbase(njobs), qslot_query(nqslots);
-        for (int t = 0; t < ntiles; ++t) {
-            const int q0 = t * qt;
-            const int tn = (int)std::min<int64_t>(qt, (int64_t)nq - q0);
-            for (int u = 0; u < qt; ++u) {
-                const int qi = std::min<int>(q0 + u, (int)nq - 1);
-                qslot_query[t * qt + u] = qi;
-                qslot_outbase[t * qt + u] = (int64_t)qi * ix->nlist;
-            }
-            for (int c = 0; c < nchunk; ++c) {
-                const int jid = t * nchunk + c;
-                databaseg[jid] = 0;
-                gstart[jid] = (int32_t)(c * chunk);
-                gcount[jid] = (int32_t)std::min<int64_t>(chunk, cgroups - c * chunk);
-                rows[jid] = (int32_t)ix->nlist;
-                jnq[jid] = tn;
-                qbase[jid] = t * qt;
-            }
-        }
-        const size_t b64 = sizeof(int64_t), b32 = sizeof(int32_t);
-        auto al8 = [](size_t b) { return (b + 7) & ~7ull; };
-        size_t need = al8(njobs * b64) + 5 * al8(njobs * b32) +
-                      al8(nqslots * b32) + al8(nqslots * b64);
-        cx->w_jobs.ensure(need);
-        uint8_t* p = cx->w_jobs.as<uint8_t>();
-        ScanJobs jb;
-        auto up = [&](const void* src, size_t bytes) {
-            HIP_CHECK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s));
-            void* r = p;
-            p += (bytes + 7) & ~7ull;
-            return r;
-        };
-        jb.databaseg = (int64_t*)up(databaseg.data(), njobs * b64);
-        jb.gstart = (int32_t*)up(gstart.data(), njobs * b32);
-        jb.gcount = (int32_t*)up(gcount.data(), njobs * b32);
-        jb.rows = (int32_t*)up(rows.data(), njobs * b32);
-        jb.nq = (int32_t*)up(jnq.data(), njobs * b32);
-        jb.qbase = (int32_t*)up(qbase.data(), njobs * b32);
-        jb.qslot_query = (int32_t*)up(qslot_query.data(), nqslots * b32);
-        jb.qslot_outbase = (int64_t*)up(qslot_outbase.data(), nqslots * b64);
-        jb.slot_base = nullptr;
-        jb.njobs = njobs;
-        HIP_CHECK(hipEventRecord(cx->ev[0], s));
-        launch_scan(ix->kmetric, qt, ix->d_cent_packed, d_q, d_qn, dpad, jb,
-                    cx->w_cdists.as<float>(), s);
-        KCHECK("rank-scan");
-        HIP_CHECK(hipEventRecord(cx->ev[1], s));
-        cx->w_csel_slots.ensure((size_t)nq * probe * 4);
-        cx->w_csel_dists.ensure((size_t)nq * probe * 4);
-        launch_topk(cx->w_cdists.as<float>(), nullptr, ix->nlist, (int)nq,
-                    (int)probe, cx->w_csel_slots.as<int32_t>(),
-                    cx->w_csel_dists.as<float>(), s);
-        KCHECK("rank-topk");
-    }
-
-    /* 3. D2H the probe selection; build list-scan jobs on the host
-     * (findCentroids -> scanEntries shape, search.go:917-1005). */
-    std::vector<int32_t> h_probe((size_t)nq * probe);
-    HIP_CHECK(hipMemcpyAsync(h_probe.data(), cx->w_csel_slots.ptr,
-                             h_probe.size() * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(hipGetLastError());
-
-    std::vector<int64_t> probe_offs((size_t)nq * (probe + 1));
-    std::vector<int64_t> qoffs(nq + 1, 0);
-    for (uint64_t q = 0; q < nq; ++q) {
-        int64_t acc = 0;
-        probe_offs[q * (probe + 1)] = 0;
-        for (uint32_t r = 0; r < probe; ++r) {
-            const int32_t l = h_probe[q * probe + r];
-            if (l >= 0) acc += ix->list_rows[l];
-            probe_offs[q * (probe + 1) + r + 1] = acc;
-        }
-        qoffs[q + 1] = qoffs[q] + acc;
-    }
-    const int64_t total_cand = qoffs[nq];
-
-    /* group (query, rank) pairs by list */
-    std::vector<int32_t> lcount(ix->nlist, 0);
-    for (uint64_t q = 0; q < nq; ++q)
-        for (uint32_t r = 0; r < probe; ++r) {
-            const int32_t l = h_probe[q * probe + r];
-            if (l >= 0 && ix->list_rows[l] > 0) lcount[l]++;
-        }
-    std::vector<int64_t> lbase(ix->nlist + 1, 0);
-    for (uint32_t l = 0; l < ix->nlist; ++l) lbase[l + 1] = lbase[l] + lcount[l];
-    const int64_t npairs = lbase[ix->nlist];
-    std::vector<int32_t> pair_q(npairs);
-    std::vector<int64_t> pair_ob(npairs);
-    {
-        std::vector<int64_t> cursor(lbase.begin(), lbase.end() - 1);
-        for (uint64_t q = 0; q < nq; ++q)
-            for (uint32_t r = 0; r < probe; ++r) {
-                const int32_t l = h_probe[q * probe + r];
-                if (l < 0 || ix->list_rows[l] == 0) continue;
-                const int64_t pos = cursor[l]++;
-                pair_q[pos] = (int32_t)q;
-                pair_ob[pos] = qoffs[q] + probe_offs[q * (probe + 1) + r];
-            }
-    }
-
-    /* jobs: per list, query tiles of qt x group CHUNKS.
-     * Chunking serves two ends at once:
-     *  - tail balance: a job is <= ~3.5 MB of list data, so hub lists
-     *    (many rows AND many query tiles) become many small jobs instead
-     *    of one straggler workgroup;
-     *  - L2 reuse: jobs are emitted chunk-OUTER, tile-INNER, and the
-     *    XCD-aware remap in the kernel gives each XCD a contiguous job
-     *    range — so the ~96 co-resident jobs of an XCD are different
-     *    query tiles over the SAME <=3.5 MB chunk (< 4 MB per-XCD L2),
-     *    and the tile re-read multiplicity is served from L2, not HBM.
-     * CHUNK_G=8 groups = 8*64 rows * dpad*4 B (1.5 MB at dpad=768; measured best
-     * of {6,8,10,12,14,18,36} end-to-end — small chunks also win on tail
-     * balance);
-     * MOANN_CHUNKG overrides for tuning. */
-    static const int64_t CHUNK_G_BASE = [] {
-        const char* e = getenv("MOANN_CHUNKG");
-        const int v = e ? atoi(e) : 0;
-        return (int64_t)(v > 0 ? v : 8);
-    }();
-    /* the chunk target is BYTES (~1.5 MB of list data); narrow storage
-     * packs more rows per byte, so scale the group count accordingly */
-    const int64_t chunk_scale =
-        ix->qtype == Quantization_F32 ? 1
-        : (ix->qtype == Quantization_F16 || ix->qtype == Quantization_BF16)
-            ? 2
-            : 4;
-    const int64_t CHUNK_G = CHUNK_G_BASE * chunk_scale;
-
-    std::vector<int64_t> databaseg, qslot_outbase, jslot_base;
-    std::vector<int32_t> gstart, gcount, rows, jnq, qbase, qslot_query;
-    std::vector<int32_t> tile_qb, tile_nq; /* per-tile scratch, reused */
-    for (uint32_t l = 0; l < ix->nlist; ++l) {
-        if (!lcount[l]) continue;
-        const int64_t lg = (ix->list_rows[l] + 63) / 64;
-        tile_qb.clear();
-        tile_nq.clear();
-        for (int64_t t0 = 0; t0 < lcount[l]; t0 += qt) {
-            const int tn = (int)std::min<int64_t>(qt, lcount[l] - t0);
-            tile_qb.push_back((int32_t)qslot_query.size());
-            tile_nq.push_back(tn);
-            for (int u = 0; u < qt; ++u) {
-                const int64_t pi = lbase[l] + t0 + std::min<int64_t>(u, tn - 1);
-                qslot_query.push_back(pair_q[pi]);
-                qslot_outbase.push_back(pair_ob[pi]);
-            }
-        }
-        for (int64_t g0 = 0; g0 < lg; g0 += CHUNK_G)
-            for (size_t ti = 0; ti < tile_qb.size(); ++ti) {
-                jslot_base.push_back(ix->list_slot_base[l]);
-                databaseg.push_back(ix->list_gbase[l]);
-                gstart.push_back((int32_t)g0);
-                gcount.push_back((int32_t)std::min<int64_t>(CHUNK_G, lg - g0));
-                rows.push_back(ix->list_rows[l]);
-                jnq.push_back(tile_nq[ti]);
-                qbase.push_back(tile_qb[ti]);
-            }
-    }
-    const int njobs = (int)databaseg.size();
-    const int nqslots = (int)qslot_query.size();
-
-    /* 4. list scan into the ragged candidate buffer */
-    const bool narrow = ix->qtype != Quantization_F32;
-    const bool uns = ix->qtype == Quantization_UINT8;
-    const bool half = ix->qtype == Quantization_F16 ||
-                      ix->qtype == Quantization_BF16;
-    const bool use_refine = refine_scan;
-    const uint32_t* d_filter = nullptr;
-    if (filter_words) {
-        const size_t fw = (size_t)((ix->count + 31) / 32);
-        cx->h_filter.assign(filter_words, filter_words + fw);
-        cx->w_filter.ensure(fw * 4);
-        HIP_CHECK(hipMemcpyAsync(cx->w_filter.ptr, cx->h_filter.data(),
-                                 fw * 4, hipMemcpyHostToDevice, s));
-        d_filter = cx->w_filter.as<uint32_t>();
-    }
-    cx->w_cand.ensure(std::max<int64_t>(1, total_cand) * 4);
-    {
-        const size_t b64 = sizeof(int64_t), b32 = sizeof(int32_t);
-        auto al8 = [](size_t b) { return (b + 7) & ~7ull; };
-        size_t need = 2 * al8((size_t)njobs * b64) + 5 * al8((size_t)njobs * b32) +
-                      al8((size_t)nqslots * b32) + al8((size_t)nqslots * b64) + 64;
-        cx->w_qslots.ensure(need);
-        uint8_t* p = cx->w_qslots.as<uint8_t>();
-        auto up = [&](const void* src, size_t bytes) {
-            void* r = p;
-            if (bytes)
-                HIP_CHECK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s));
-            p += (bytes + 7) & ~7ull;
-            return r;
-        };
-        ScanJobs jb;
-        jb.databaseg = (int64_t*)up(databaseg.data(), njobs * b64);
-        jb.gstart = (int32_t*)up(gstart.data(), njobs * b32);
-        jb.gcount = (int32_t*)up(gcount.data(), njobs * b32);
-        jb.rows = (int32_t*)up(rows.data(), njobs * b32);
-        jb.nq = (int32_t*)up(jnq.data(), njobs * b32);
-        jb.qbase = (int32_t*)up(qbase.data(), njobs * b32);
-        jb.qslot_query = (int32_t*)up(qslot_query.data(), nqslots * b32);
-        jb.qslot_outbase = (int64_t*)up(qslot_outbase.data(), nqslots * b64);
-        jb.slot_base = (int64_t*)up(jslot_base.data(), njobs * b64);
-        jb.njobs = njobs;
-        HIP_CHECK(hipEventRecord(cx->ev[2], s));
-        if (use_refine) {
-            /* byte first pass over the internal clip-quantized image */
-            cx->w_queries_q.ensure((size_t)nq * dpad);
-            launch_quantize_rows(false, d_q, (int64_t)nq, dpad, (int)ix->dim,
-                                 dpad, (float)ix->rq_mul, (float)ix->rq_add,
-                                 cx->w_queries_q.as<uint8_t>(), s);
-            KCHECK("refine-query-quantize");
-            const int32_t* d_qni = nullptr;
-            if (ix->kmetric == KM_COS || ix->kmetric == KM_L2SQ) {
-                cx->w_qnorms_i.ensure(nq * 4);
-                launch_qnorms_i8(false, cx->w_queries_q.as<uint8_t>(),
-                                 (int)nq, dpad,
-                                 cx->w_qnorms_i.as<int32_t>(), s);
-                d_qni = cx->w_qnorms_i.as<int32_t>();
-            }
-            launch_scan_i8(ix->kmetric, false, ix->d_packed_rq,
-                           cx->w_queries_q.as<uint8_t>(), d_qni,
-                           ix->d_rownorm_rq, dpad, jb,
-                           cx->w_cand.as<float>(), s, d_filter, qt);
-        } else if (half) {
-            /* plain-cast narrow search: query cast RTNE like the entries
-             * (relation_search.go:56-63), decoded-f32 distance */
-            cx->w_queries_q.ensure((size_t)nq * dpad * 2);
-            launch_quantize_half_rows(ix->qtype == Quantization_BF16, d_q,
-                                      (int64_t)nq, dpad, (int)ix->dim, dpad,
-                                      cx->w_queries_q.as<uint16_t>(), s);
-            KCHECK("query-half-cast");
-            const float* d_qnh = nullptr;
-            if (ix->kmetric == KM_COS) {
-                cx->w_qnorms_i.ensure(nq * 4);
-                launch_qnorms_h(ix->qtype == Quantization_BF16,
-                                cx->w_queries_q.as<uint16_t>(), (int)nq,
-                                dpad, cx->w_qnorms_i.as<float>(), s);
-                d_qnh = cx->w_qnorms_i.as<float>();
-            }
-            launch_scan_h(ix->kmetric, ix->qtype == Quantization_BF16,
-                          (const uint16_t*)ix->d_packed_q,
-                          cx->w_queries_q.as<uint16_t>(), d_qnh, dpad, jb,
-                          cx->w_cand.as<float>(), s, d_filter);
-        } else if (narrow) {
-            /* quantize the padded f32 queries with the entry map (the
-             * search_quantize contract: query narrowed the same way as the
-             * entries — quantizer.go ApplyInt8/entry SQL) */
-            cx->w_queries_q.ensure((size_t)nq * dpad);
-            launch_quantize_rows(uns, d_q, (int64_t)nq, dpad, (int)ix->dim,
-                                 dpad, (float)ix->quant_mul,
-                                 (float)ix->quant_add,
-                                 cx->w_queries_q.as<uint8_t>(), s);
-            KCHECK("query-quantize");
-            const int32_t* d_qni = nullptr;
-            if (ix->kmetric == KM_COS || ix->kmetric == KM_L2SQ) {
-                /* cos denominators; also qn of the dot-form L2 */
-                cx->w_qnorms_i.ensure(nq * 4);
-                launch_qnorms_i8(uns, cx->w_queries_q.as<uint8_t>(), (int)nq,
-                                 dpad, cx->w_qnorms_i.as<int32_t>(), s);
-                d_qni = cx->w_qnorms_i.as<int32_t>();
-            }
-            launch_scan_i8(ix->kmetric, uns, ix->d_packed_q,
-                           cx->w_queries_q.as<uint8_t>(), d_qni,
-                           ix->d_rownorm_q, dpad, jb,
-                           cx->w_cand.as<float>(), s, d_filter, qt);
-        } else {
-            launch_scan(ix->kmetric, qt, ix->d_packed, d_q, d_qn, dpad, jb,
-                        cx->w_cand.as<float>(), s, d_filter);
-        }
-        KCHECK("list-scan");
-        HIP_CHECK(hipEventRecord(cx->ev[3], s));
-    }
-
-    /* 5. per-query top-limit + id gather + transform */
-    cx->w_qoffs.ensure((nq + 1) * 8);
-    HIP_CHECK(hipMemcpyAsync(cx->w_qoffs.ptr, qoffs.data(), (nq + 1) * 8,
-                             hipMemcpyHostToDevice, s));
-    cx->w_probe_lists.ensure((size_t)nq * probe * 4);
-    cx->w_probe_offs.ensure(probe_offs.size() * 8);
-    HIP_CHECK(hipMemcpyAsync(cx->w_probe_lists.ptr, h_probe.data(),
-                             h_probe.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(cx->w_probe_offs.ptr, probe_offs.data(),
-                             probe_offs.size() * 8, hipMemcpyHostToDevice, s));
-    cx->w_sel_slots.ensure((size_t)nq * limit * 4);
-    cx->w_sel_dists.ensure((size_t)nq * limit * 4);
-    HIP_CHECK(hipEventRecord(cx->ev[4], s));
-    if (use_refine) {
-        /* top-R by byte distance -> exact f32 re-rank -> top-limit */
-        const int R = std::max<int>((int)limit, ix->refine_depth);
-        cx->w_rsel_slots.ensure((size_t)nq * R * 4);
-        cx->w_rsel_dists.ensure((size_t)nq * R * 4);
-        launch_topk(cx->w_cand.as<float>(), cx->w_qoffs.as<int64_t>(), 0,
-                    (int)nq, R, cx->w_rsel_slots.as<int32_t>(),
-                    cx->w_rsel_dists.as<float>(), s);
-        KCHECK("refine-topR");
-        cx->w_refined.ensure((size_t)nq * R * 4);
-        launch_refine(ix->kmetric, ix->d_rows_f32, d_q, d_qn, (int)ix->dim,
-                      dpad, R, (int)nq, cx->w_rsel_slots.as<int32_t>(),
-                      cx->w_rsel_dists.as<float>(),
-                      cx->w_probe_lists.as<int32_t>(),
-                      cx->w_probe_offs.as<int64_t>(), ix->d_list_slot_base,
-                      (int)probe, cx->w_refined.as<float>(), s);
-        KCHECK("refine");
-        cx->w_sel2.ensure((size_t)nq * limit * 4);
-        launch_topk(cx->w_refined.as<float>(), nullptr, R, (int)nq,
-                    (int)limit, cx->w_sel2.as<int32_t>(),
-                    cx->w_sel_dists.as<float>(), s);
-        KCHECK("refine-topk");
-        launch_compose_select(cx->w_sel2.as<int32_t>(),
-                              cx->w_rsel_slots.as<int32_t>(), R, (int)limit,
-                              (int)nq, cx->w_sel_slots.as<int32_t>(), s);
-        KCHECK("refine-compose");
-    } else {
-        launch_topk(cx->w_cand.as<float>(), cx->w_qoffs.as<int64_t>(), 0,
-                    (int)nq, (int)limit, cx->w_sel_slots.as<int32_t>(),
-                    cx->w_sel_dists.as<float>(), s);
-        KCHECK("cand-topk");
-    }
-    HIP_CHECK(hipEventRecord(cx->ev[5], s));
-    cx->w_out_ids.ensure((size_t)nq * limit * 8);
-    cx->w_out_dists.ensure((size_t)nq * limit * 4);
-    launch_gather(cx->w_sel_slots.as<int32_t>(), cx->w_sel_dists.as<float>(),
-                  cx->w_probe_lists.as<int32_t>(),
-                  cx->w_probe_offs.as<int64_t>(), ix->d_list_slot_base,
-                  ix->d_id_by_slot, (int)probe, (int)nq, (int)limit, do_sqrt,
-                  inv_mul2, cx->w_out_ids.as<int64_t>(),
-                  cx->w_out_dists.as<float>(), s);
-    KCHECK("gather");
-    /* D2H through the ctx's pinned bounce (pageable-async degrades to a
-     * host-blocking copy on ROCm, which would serialize the pipeline) */
-    cx->ensure_hout((size_t)nq * limit * 12);
-    int64_t* ho_ids = (int64_t*)cx->h_out;
-    float* ho_dists = (float*)(ho_ids + (size_t)nq * limit);
-    HIP_CHECK(hipMemcpyAsync(ho_ids, cx->w_out_ids.ptr,
-                             (size_t)nq * limit * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(ho_dists, cx->w_out_dists.ptr,
-                             (size_t)nq * limit * 4, hipMemcpyDeviceToHost, s));
+    stage_queries(ix, cx, queries, queries_on_device);
+    rank_centroids(ix, cx);
+    fetch_probe_and_plan(ix, cx);
+    scan_lists(ix, cx, filter_words);
+    select_candidates(ix, cx);
+    gather_results(ix, cx);
 
     /* host-known perf counters (kernel window times land at collect) */
     ix->perf.c.rank_launches++;
     ix->perf.c.rank_flops += 2ull * nq * ix->nlist * ix->dim;
     uint64_t unique_rows = 0;
     for (uint32_t l = 0; l < ix->nlist; ++l)
-        if (lcount[l]) unique_rows += (uint64_t)ix->list_rows[l];
+        if (cx->lists.lcount[l]) unique_rows += (uint64_t)ix->list_rows[l];
     ix->perf.c.scan_launches++;
     ix->perf.c.scan_bytes += unique_rows * ix->dim * 4;
-    ix->perf.c.scan_rows += (uint64_t)total_cand;
+    ix->perf.c.scan_rows += (uint64_t)cx->offs.total_cand;
 
     res->owner = cx;
     res->collected = false;
     HIP_CHECK(hipEventCreate(&res->done_ev));
-    HIP_CHECK(hipEventRecord(res->done_ev, s));
+    HIP_CHECK(hipEventRecord(res->done_ev, cx->stream));
     cx->pending = res.get();
     /* submit-side wall: under pipelining this is the NON-overlapped host
      * cost (H2D, probe sync, job build); kernel windows come from cx->ev */
-    if (sync_end) {
-        const double kms = collect_result(res.get());
-        const double wall = std::chrono::duration<double, std::milli>(
-            std::chrono::steady_clock::now() - t_all0).count();
-        ix->perf.c.other_ms += wall - kms;
-    } else {
-        const double wall = std::chrono::duration<double, std::milli>(
-            std::chrono::steady_clock::now() - t_all0).count();
-        ix->perf.c.other_ms += wall;
-    }
+    const double kms = sync_end ? collect_result(res.get()) : 0.0;
+    const double wall = std::chrono::duration<double, std::milli>(
+        std::chrono::steady_clock::now() - t_all0).count();
+    ix->perf.c.other_ms += wall - kms;
     return res;
 }
 

@@ -22,7 +22,6 @@
 
 #include "../../include/moann.h"
 #include "moann_host_common.h"
-#include "moann_internal.h"
 
 namespace moann {
 void launch_pq_scan_q(const uint8_t* codes, const float* atab,
@@ -42,10 +41,6 @@ void launch_pq_tables(const float* cents, const float* queries,
                       const float* cb, int nsub, int sd, int dpad,
                       int64_t nlist_or_nq, bool btab_mode, float* out,
                       hipStream_t stream);
-void launch_pq_pack(const uint8_t* codes_rowmajor, int nsub,
-                    const int64_t* group_rowbase, const int32_t* group_valid,
-                    const int64_t* slot_rows, int64_t ngroups, uint8_t* packed,
-                    hipStream_t stream);
 }
 
 namespace {
@@ -86,6 +81,8 @@ struct PqIndex {
     MoannDevBuf w_queries, w_cdists, w_csel_slots, w_csel_dists, w_jobs;
     MoannDevBuf w_cand, w_sel_slots, w_sel_dists, w_probe_lists, w_probe_offs;
     MoannDevBuf w_qoffs, w_out_ids, w_out_dists, w_atab, w_qn, w_filter;
+    HostScanJobs rank_jobs; /* host plan scratch, reused across searches */
+    ProbeOffsets offs;
 
     std::mutex mu;
     moann_perf_t perf {};
@@ -130,77 +127,19 @@ std::unique_ptr<MoannResult> pq_search(PqIndex* ix, const float* queries,
         ix->ev_made = true;
     }
 
-    /* queries padded to device */
-    ix->w_queries.ensure((size_t)nq * dpad * 4);
-    if ((int)ix->dim != dpad)
-        MOANN_HIP_CHECK(hipMemsetAsync(ix->w_queries.ptr, 0,
-                                       (size_t)nq * dpad * 4, s));
-    MOANN_HIP_CHECK(hipMemcpy2DAsync(
-        ix->w_queries.ptr, (size_t)dpad * 4, queries, (size_t)ix->dim * 4,
-        (size_t)ix->dim * 4, nq,
-        on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    const float* d_q = ix->w_queries.as<float>();
+    const float* d_q = stage_padded_queries(ix->w_queries, queries, on_device,
+                                            nq, ix->dim, ix->dpad, s);
 
     /* 1. coarse rank: interleaved scan over the centroid matrix (shared
      * kernel; f32 L2sq — config-5 is L2) + top-probe */
     {
         ix->w_cdists.ensure((size_t)nq * ix->nlist * 4);
-        const int qt = 8;
-        const int ntiles = (int)((nq + qt - 1) / qt);
-        const int64_t cgroups = ix->cent_groups;
-        int64_t want_chunks = std::min<int64_t>(
-            cgroups, std::max<int64_t>(1, (1024 + ntiles - 1) / ntiles));
-        const int chunk = (int)((cgroups + want_chunks - 1) / want_chunks);
-        const int nchunk = (int)((cgroups + chunk - 1) / chunk);
-        const int njobs = ntiles * nchunk;
-        const int nqslots = ntiles * qt;
-        std::vector<int64_t> databaseg(njobs), qslot_outbase(nqslots);
-        std::vector<int32_t> gstart(njobs), gcount(njobs), rows(njobs),
-            jnq(njobs), qbase(njobs), qslot_query(nqslots);
-        for (int t = 0; t < ntiles; ++t) {
-            const int q0 = t * qt;
-            const int tn = (int)std::min<int64_t>(qt, (int64_t)nq - q0);
-            for (int u = 0; u < qt; ++u) {
-                const int qi = std::min<int>(q0 + u, (int)nq - 1);
-                qslot_query[t * qt + u] = qi;
-                qslot_outbase[t * qt + u] = (int64_t)qi * ix->nlist;
-            }
-            for (int c = 0; c < nchunk; ++c) {
-                const int jid = t * nchunk + c;
-                databaseg[jid] = 0;
-                gstart[jid] = (int32_t)(c * chunk);
-                gcount[jid] =
-                    (int32_t)std::min<int64_t>(chunk, cgroups - c * chunk);
-                rows[jid] = (int32_t)ix->nlist;
-                jnq[jid] = tn;
-                qbase[jid] = t * qt;
-            }
-        }
-        const size_t b64 = 8, b32 = 4;
-        auto al8 = [](size_t b) { return (b + 7) & ~7ull; };
-        ix->w_jobs.ensure(al8(njobs * b64) + 5 * al8(njobs * b32) +
-                          al8(nqslots * b32) + al8(nqslots * b64) + 64);
-        uint8_t* p = ix->w_jobs.as<uint8_t>();
-        auto up = [&](const void* src, size_t bytes) {
-            void* r = p;
-            if (bytes)
-                MOANN_HIP_CHECK(hipMemcpyAsync(p, src, bytes,
-                                               hipMemcpyHostToDevice, s));
-            p += (bytes + 7) & ~7ull;
-            return r;
-        };
-        ScanJobs jb;
-        jb.databaseg = (int64_t*)up(databaseg.data(), njobs * b64);
-        jb.gstart = (int32_t*)up(gstart.data(), njobs * b32);
-        jb.gcount = (int32_t*)up(gcount.data(), njobs * b32);
-        jb.rows = (int32_t*)up(rows.data(), njobs * b32);
-        jb.nq = (int32_t*)up(jnq.data(), njobs * b32);
-        jb.qbase = (int32_t*)up(qbase.data(), njobs * b32);
-        jb.qslot_query = (int32_t*)up(qslot_query.data(), nqslots * b32);
-        jb.qslot_outbase = (int64_t*)up(qslot_outbase.data(), nqslots * b64);
-        jb.slot_base = nullptr;
-        jb.njobs = njobs;
-        launch_scan(KM_L2SQ, 8, ix->d_cent_packed, d_q, nullptr, dpad, jb,
+        /* the compiler-scheduled f32 scan at its LDS-safe default width */
+        const ScanVariant rank {ScanKind::F32, 8};
+        plan_rank_scan(nq, rank.qt, ix->nlist, ix->cent_groups,
+                       ix->rank_jobs);
+        const ScanJobs jb = upload_scan_jobs(ix->rank_jobs, ix->w_jobs, s);
+        launch_scan(KM_L2SQ, rank, ix->d_cent_packed, d_q, nullptr, dpad, jb,
                     ix->w_cdists.as<float>(), s);
         MOANN_KCHECK("pq-rank-scan");
         ix->w_csel_slots.ensure((size_t)nq * probe * 4);
@@ -219,33 +158,14 @@ std::unique_ptr<MoannResult> pq_search(PqIndex* ix, const float* queries,
     MOANN_HIP_CHECK(hipStreamSynchronize(s));
     MOANN_HIP_CHECK(hipGetLastError());
 
-    std::vector<int64_t> probe_offs((size_t)nq * (probe + 1));
-    std::vector<int64_t> qoffs(nq + 1, 0);
-    for (uint64_t q = 0; q < nq; ++q) {
-        int64_t acc = 0;
-        probe_offs[q * (probe + 1)] = 0;
-        for (uint32_t r = 0; r < probe; ++r) {
-            const int32_t l = h_probe[q * probe + r];
-            if (l >= 0) acc += ix->list_rows[l];
-            probe_offs[q * (probe + 1) + r + 1] = acc;
-        }
-        qoffs[q + 1] = qoffs[q] + acc;
-    }
-    const int64_t total_cand = qoffs[nq];
+    plan_probe_offsets(h_probe.data(), nq, probe, ix->list_rows, ix->offs);
+    const int64_t total_cand = ix->offs.total_cand;
 
     ix->w_cand.ensure(std::max<int64_t>(1, total_cand) * 4);
     /* offsets to device BEFORE the scan (the per-query kernel walks them) */
-    ix->w_qoffs.ensure((nq + 1) * 8);
-    MOANN_HIP_CHECK(hipMemcpyAsync(ix->w_qoffs.ptr, qoffs.data(),
-                                   (nq + 1) * 8, hipMemcpyHostToDevice, s));
-    ix->w_probe_lists.ensure((size_t)nq * probe * 4);
-    ix->w_probe_offs.ensure(probe_offs.size() * 8);
-    MOANN_HIP_CHECK(hipMemcpyAsync(ix->w_probe_lists.ptr, h_probe.data(),
-                                   h_probe.size() * 4, hipMemcpyHostToDevice,
-                                   s));
-    MOANN_HIP_CHECK(hipMemcpyAsync(ix->w_probe_offs.ptr, probe_offs.data(),
-                                   probe_offs.size() * 8,
-                                   hipMemcpyHostToDevice, s));
+    upload_vector(ix->w_qoffs, ix->offs.qoffs, s);
+    upload_vector(ix->w_probe_lists, h_probe, s);
+    upload_vector(ix->w_probe_offs, ix->offs.probe_offs, s);
     {
         /* per-query A table + |q|^2 for this batch (row_b / |c|^2 are
          * build-time; -2(q.c_l) falls out of the rank stage's distances) */
