@@ -26,6 +26,7 @@
 #include <cstdint>
 
 #include "moann_internal.h"
+#include "moann_scan_device.h" /* mo_cos_distance, slot_passes */
 
 namespace moann {
 
@@ -80,11 +81,7 @@ __device__ float wave_dist(const float* __restrict__ vecs, int64_t slot,
     }
     if (METRIC == U_L2SQ) return dot;
     if (METRIC == U_IP) return 1.0f - dot;
-    double denom = sqrt((double)nrm) * sqrt((double)qnorm);
-    if (denom == 0.0) return 1.0f;
-    double sim = (double)dot / denom;
-    sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-    return (float)(1.0 - sim);
+    return mo_cos_distance(dot, nrm, qnorm);
 }
 
 template <int METRIC, bool FILTERED>
@@ -186,7 +183,7 @@ __global__ __launch_bounds__(1024) void hnsw_search_kernel(
      * filtered candidates interleave the passing front). */
     const auto passes = [&](int64_t slot) -> bool {
         if (!FILTERED) return true;
-        return (slot_filter[slot >> 5] >> (slot & 31)) & 1u;
+        return slot_passes(slot_filter, slot);
     };
     if (tid == 0) {
         const int64_t w = cur >> 5;

@@ -29,6 +29,7 @@
 #include <cstdint>
 
 #include "moann_internal.h"
+#include "moann_scan_device.h" /* scan_job_index, mo_cos_distance */
 
 namespace moann {
 
@@ -54,15 +55,7 @@ __global__ __launch_bounds__(256) void rank_gemm_kernel(
     const int tiles_c = (nlist + 31) / 32;
     /* XCD-aware contiguous remap: consecutive jobs in one XCD share the
      * centroid macro-column, so the 32-row C slab re-reads are L2-served */
-    int macro;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        macro = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8)
-                + idx;
-        if (macro >= nwg) macro = bid;
-    }
+    const int macro = scan_job_index();
     const int mrow = macro / tiles_c, mcol = macro % tiles_c;
     const int qbase = mrow * 32, cbase = mcol * 32;
     if (qbase >= nq || cbase >= nlist) return;
@@ -133,14 +126,7 @@ __global__ __launch_bounds__(256) void rank_gemm_kernel(
         if (METRIC == KM_IP) {
             dist = -dot;
         } else if (METRIC == KM_COS) {
-            const double denom =
-                sqrt((double)cnorms[ocol]) * sqrt((double)qnorms[orow]);
-            if (denom == 0.0) dist = 1.0f;
-            else {
-                double sim = (double)dot / denom;
-                sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-                dist = (float)(1.0 - sim);
-            }
+            dist = mo_cos_distance(dot, cnorms[ocol], qnorms[orow]);
         } else { /* KM_L2SQ: expanded form */
             dist = qnorms[orow] + cnorms[ocol] - 2.0f * dot;
             if (dist < 0.f) dist = 0.f;

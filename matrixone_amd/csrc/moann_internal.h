@@ -11,7 +11,9 @@
 
 namespace moann {
 
-/* One scan job: a (list segment, query tile) pair. SoA device arrays. */
+/* One scan job: a (list segment, query tile) pair. SoA device arrays; the
+ * scan kernels take the whole table as one by-value argument and read their
+ * row of it through JobView (moann_scan_device.h). */
 struct ScanJobs {
     const int64_t* databaseg;  /* [njobs] base group index of the list       */
     const int32_t* gstart;     /* [njobs] first group (list-relative)        */

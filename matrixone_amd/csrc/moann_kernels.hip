@@ -26,12 +26,26 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "moann_internal.h"
+#include "moann_scan_device.h"
 
 namespace moann {
 
 #define WAVE 64
+
+/* Run f with the metric as a compile-time constant:
+ * f(std::integral_constant<int, KM_...>{}). */
+template <typename F>
+static void with_metric(int metric, F&& f) {
+    switch (metric) {
+    case KM_L2SQ: f(std::integral_constant<int, KM_L2SQ>{}); break;
+    case KM_IP:   f(std::integral_constant<int, KM_IP>{}); break;
+    case KM_COS:  f(std::integral_constant<int, KM_COS>{}); break;
+    default:      f(std::integral_constant<int, KM_L1>{}); break;
+    }
+}
 
 /* monotone float -> u32 key (ascending order preserved) */
 __device__ __forceinline__ uint32_t f2u(float f) {
@@ -49,162 +63,47 @@ __device__ __forceinline__ float u2f(uint32_t u) {
  * 16 B data quads (halves LDS traffic per byte). Per j4 step and query:
  * 8 fma-class VALU ops per 32 B/lane -> VALU ceiling ~19 TB/s equivalent,
  * comfortably above the ~6.3 TB/s HBM bound this kernel targets. */
-template <int METRIC, int QT, int GP>
+template <int METRIC, int QT>
 __global__ __launch_bounds__(256) void scan_kernel(
     const float* __restrict__ packed, const float* __restrict__ queries,
-    const float* __restrict__ qnorms, int dpad,
-    const int64_t* __restrict__ j_databaseg,
-    const int32_t* __restrict__ j_gstart, const int32_t* __restrict__ j_gcount,
-    const int32_t* __restrict__ j_rows, const int32_t* __restrict__ j_nq,
-    const int32_t* __restrict__ j_qbase,
-    const int32_t* __restrict__ qslot_query,
-    const int64_t* __restrict__ qslot_outbase,
-    const int64_t* __restrict__ j_slot_base,
-    const uint32_t* __restrict__ filter_bitset, /* bit per GLOBAL slot; a
-        cleared bit excludes the entry (cuVS bitset_filter precedent,
-        cgo/cuvs/ivf_flat.hpp:908-924); null = unfiltered */
+    const float* __restrict__ qnorms, int dpad, const ScanJobs jobs,
+    const uint32_t* __restrict__ filter_bitset, /* null = unfiltered */
     float* __restrict__ dists_out) {
     extern __shared__ float lds[];  /* [QT][dpad] (+[QT] qnorm for cos) */
     float* ldsq = lds;
     float* ldsn = lds + QT * dpad;
 
-    /* XCD-aware bijective blockIdx remap (T1): the dispatcher places block
-     * b on XCD b%8; this permutation gives each XCD a CONTIGUOUS job range,
-     * so the query tiles of one list (consecutive jobs) stream through one
-     * XCD's L2 instead of re-fetching from HBM on every XCD. */
-    int j;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        j = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-        if (j >= nwg) j = bid; /* safety: cannot happen for bijective map */
-    }
-    const int nq = j_nq[j];
-    const int qbase = j_qbase[j];
-
-    for (int t = 0; t < QT; ++t) {
-        if (t < nq) {
-            const int q = qslot_query[qbase + t];
-            const float* src = queries + (int64_t)q * dpad;
-            for (int e = threadIdx.x; e < dpad; e += blockDim.x)
-                ldsq[t * dpad + e] = src[e];
-            if (METRIC == KM_COS && threadIdx.x == 0) ldsn[t] = qnorms[q];
-        } else {
-            for (int e = threadIdx.x; e < dpad; e += blockDim.x)
-                ldsq[t * dpad + e] = 0.f;
-            if (METRIC == KM_COS && threadIdx.x == 0) ldsn[t] = 0.f;
-        }
-    }
-    __syncthreads();
+    const JobView jv = load_job(jobs);
+    stage_query_tile<QT, METRIC == KM_COS>(jv, jobs.qslot_query, queries,
+                                           qnorms, dpad, ldsq, ldsn);
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gstart = j_gstart[j], gcount = j_gcount[j];
-    const int rows = j_rows[j];
-    const int64_t baseg = j_databaseg[j];
+    const int gend = jv.gstart + jv.gcount;
     const int d4 = dpad >> 2;
 
-    /* GP=2: each wave walks ADJACENT group pairs (one LDS broadcast feeds
-     * 32 B of data — best for QT<=8). GP=1: one group per wave — half the
-     * live registers, which is what lets hipcc software-pipeline the loads
-     * at QT=16. */
-    for (int gp = gstart + GP * wave; gp < gstart + gcount; gp += 4 * GP) {
-        const int g0 = gp;
-        const bool has1 = GP == 2 && (gp + 1) < (gstart + gcount);
-        const int g1 = has1 ? gp + 1 : gp;
+    /* each wave walks ADJACENT group pairs: one LDS broadcast feeds 32 B of
+     * data */
+    for (int g0 = jv.gstart + 2 * wave; g0 < gend; g0 += 8) {
+        const bool has1 = (g0 + 1) < gend;
+        const int g1 = has1 ? g0 + 1 : g0;
         const float4* __restrict__ d0 =
-            (const float4*)(packed + (baseg + g0) * (int64_t)64 * dpad) + lane;
+            (const float4*)(packed + (jv.baseg + g0) * (int64_t)64 * dpad) + lane;
         const float4* __restrict__ d1 =
-            (const float4*)(packed + (baseg + g1) * (int64_t)64 * dpad) + lane;
+            (const float4*)(packed + (jv.baseg + g1) * (int64_t)64 * dpad) + lane;
 
         float acc0[QT], acc1[QT];
 #pragma unroll
         for (int t = 0; t < QT; ++t) acc0[t] = acc1[t] = 0.f;
         float rn0 = 0.f, rn1 = 0.f;
 
-        /* GP==1: hand-rolled 3-deep load ring in inline asm. hipcc will not
-         * software-pipeline this loop at QT=16 register pressure (it emits a
-         * full vmcnt(0) drain per iteration); the asm ring keeps 2 loads in
-         * flight across iterations with counted waits (guide rules: asm
-         * loads are invisible to hipcc's s_waitcnt bookkeeping, so the
-         * counted wait + sched_barrier(0) before the first consumer is
-         * ours). */
-        if (GP == 1) {
-            /* named ring slots (no arrays: a runtime-indexed ext_vector
-             * array goes to scratch) */
-            float4 r0, r1, r2;
-#define MOANN_ISSUE(slot, idx)                                              \
-            {                                                               \
-                const float4* ap = d0 + ((idx) < d4 ? (idx) : d4 - 1) * 64; \
-                asm volatile("global_load_dwordx4 %0, %1, off"              \
-                             : "=v"(slot) : "v"(ap));                       \
-            }
-#define MOANN_CONSUME(slot, idx)                                            \
-            {                                                               \
-                asm volatile("s_waitcnt vmcnt(2)" ::: "memory");            \
-                /* full fence (mask 0) is REQUIRED: any relaxation that     \
-                 * lets VMEM ops cross lets a ring REISSUE hoist above this \
-                 * wait, the outstanding count then under-retires and the   \
-                 * consumer reads an un-landed slot (measured: recall 0.0   \
-                 * at mask DS_READ|VMEM_READ while 1.6x "faster").          \
-                 * Counted-wait discipline = nothing crosses the wait.      */\
-                __builtin_amdgcn_sched_barrier(0);                          \
-                const float4 x0 = slot;                                     \
-                const int q4i = (idx);                                      \
-                if (METRIC == KM_COS)                                       \
-                    rn0 += x0.x * x0.x + x0.y * x0.y + x0.z * x0.z +        \
-                           x0.w * x0.w;                                     \
-                _Pragma("unroll")                                           \
-                for (int t = 0; t < QT; ++t) {                              \
-                    const float4 qv =                                       \
-                        ((const float4*)(ldsq + t * dpad))[q4i];             \
-                    if (METRIC == KM_L2SQ) {                                \
-                        float e;                                            \
-                        e = x0.x - qv.x; acc0[t] = fmaf(e, e, acc0[t]);     \
-                        e = x0.y - qv.y; acc0[t] = fmaf(e, e, acc0[t]);     \
-                        e = x0.z - qv.z; acc0[t] = fmaf(e, e, acc0[t]);     \
-                        e = x0.w - qv.w; acc0[t] = fmaf(e, e, acc0[t]);     \
-                    } else if (METRIC == KM_IP || METRIC == KM_COS) {       \
-                        acc0[t] = fmaf(x0.x, qv.x, acc0[t]);                \
-                        acc0[t] = fmaf(x0.y, qv.y, acc0[t]);                \
-                        acc0[t] = fmaf(x0.z, qv.z, acc0[t]);                \
-                        acc0[t] = fmaf(x0.w, qv.w, acc0[t]);                \
-                    } else {                                                \
-                        acc0[t] += fabsf(x0.x - qv.x) + fabsf(x0.y - qv.y) +\
-                                   fabsf(x0.z - qv.z) + fabsf(x0.w - qv.w); \
-                    }                                                       \
-                }                                                           \
-            }
-            MOANN_ISSUE(r0, 0)
-            MOANN_ISSUE(r1, 1)
-            MOANN_ISSUE(r2, 2)
-            int q4 = 0;
-            for (; q4 + 3 <= d4; q4 += 3) {
-                MOANN_CONSUME(r0, q4)
-                MOANN_ISSUE(r0, q4 + 3)
-                MOANN_CONSUME(r1, q4 + 1)
-                MOANN_ISSUE(r1, q4 + 4)
-                MOANN_CONSUME(r2, q4 + 2)
-                MOANN_ISSUE(r2, q4 + 5)
-            }
-            /* tail (<=2 iterations): drain, then consume without reissue */
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if (q4 < d4) { MOANN_CONSUME(r0, q4) }
-            if (q4 + 1 < d4) { MOANN_CONSUME(r1, q4 + 1) }
-#undef MOANN_ISSUE
-#undef MOANN_CONSUME
-        } else
 #pragma unroll 2 /* two iterations in flight: 4 dwordx4 issued together,
-                    counted vmcnt waits (hipcc pipelines the pair the same
-                    way it does for the QT=8 instantiation) */
+                    counted vmcnt waits */
         for (int q4 = 0; q4 < d4; ++q4) {
             const float4 x0 = d0[q4 * 64];
-            const float4 x1 = GP == 2 ? d1[q4 * 64] : float4 {0, 0, 0, 0};
+            const float4 x1 = d1[q4 * 64];
             if (METRIC == KM_COS) {
                 rn0 += x0.x * x0.x + x0.y * x0.y + x0.z * x0.z + x0.w * x0.w;
-                if (GP == 2)
-                    rn1 += x1.x * x1.x + x1.y * x1.y + x1.z * x1.z + x1.w * x1.w;
+                rn1 += x1.x * x1.x + x1.y * x1.y + x1.z * x1.z + x1.w * x1.w;
             }
 #pragma unroll
             for (int t = 0; t < QT; ++t) {
@@ -215,81 +114,33 @@ __global__ __launch_bounds__(256) void scan_kernel(
                     e = x0.y - qv.y; acc0[t] = fmaf(e, e, acc0[t]);
                     e = x0.z - qv.z; acc0[t] = fmaf(e, e, acc0[t]);
                     e = x0.w - qv.w; acc0[t] = fmaf(e, e, acc0[t]);
-                    if (GP == 2) {
-                        e = x1.x - qv.x; acc1[t] = fmaf(e, e, acc1[t]);
-                        e = x1.y - qv.y; acc1[t] = fmaf(e, e, acc1[t]);
-                        e = x1.z - qv.z; acc1[t] = fmaf(e, e, acc1[t]);
-                        e = x1.w - qv.w; acc1[t] = fmaf(e, e, acc1[t]);
-                    }
+                    e = x1.x - qv.x; acc1[t] = fmaf(e, e, acc1[t]);
+                    e = x1.y - qv.y; acc1[t] = fmaf(e, e, acc1[t]);
+                    e = x1.z - qv.z; acc1[t] = fmaf(e, e, acc1[t]);
+                    e = x1.w - qv.w; acc1[t] = fmaf(e, e, acc1[t]);
                 } else if (METRIC == KM_IP || METRIC == KM_COS) {
                     acc0[t] = fmaf(x0.x, qv.x, acc0[t]);
                     acc0[t] = fmaf(x0.y, qv.y, acc0[t]);
                     acc0[t] = fmaf(x0.z, qv.z, acc0[t]);
                     acc0[t] = fmaf(x0.w, qv.w, acc0[t]);
-                    if (GP == 2) {
-                        acc1[t] = fmaf(x1.x, qv.x, acc1[t]);
-                        acc1[t] = fmaf(x1.y, qv.y, acc1[t]);
-                        acc1[t] = fmaf(x1.z, qv.z, acc1[t]);
-                        acc1[t] = fmaf(x1.w, qv.w, acc1[t]);
-                    }
+                    acc1[t] = fmaf(x1.x, qv.x, acc1[t]);
+                    acc1[t] = fmaf(x1.y, qv.y, acc1[t]);
+                    acc1[t] = fmaf(x1.z, qv.z, acc1[t]);
+                    acc1[t] = fmaf(x1.w, qv.w, acc1[t]);
                 } else { /* KM_L1 */
                     acc0[t] += fabsf(x0.x - qv.x) + fabsf(x0.y - qv.y) +
                                fabsf(x0.z - qv.z) + fabsf(x0.w - qv.w);
-                    if (GP == 2)
-                        acc1[t] += fabsf(x1.x - qv.x) + fabsf(x1.y - qv.y) +
-                                   fabsf(x1.z - qv.z) + fabsf(x1.w - qv.w);
+                    acc1[t] += fabsf(x1.x - qv.x) + fabsf(x1.y - qv.y) +
+                               fabsf(x1.z - qv.z) + fabsf(x1.w - qv.w);
                 }
             }
         }
 
-        const int row0 = g0 * 64 + lane;
-        const int row1 = g1 * 64 + lane;
-        bool pass0 = true, pass1 = true;
-        if (filter_bitset) {
-            const int64_t sb = j_slot_base[j];
-            if (row0 < rows) {
-                const int64_t gs = sb + row0;
-                pass0 = (filter_bitset[gs >> 5] >> (gs & 31)) & 1u;
-            }
-            if (has1 && row1 < rows) {
-                const int64_t gs = sb + row1;
-                pass1 = (filter_bitset[gs >> 5] >> (gs & 31)) & 1u;
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            if (t >= nq) break;
-            const int64_t ob = qslot_outbase[qbase + t];
-            if (row0 < rows) {
-                float dist;
-                if (METRIC == KM_IP) dist = -acc0[t];
-                else if (METRIC == KM_COS) {
-                    /* distance_func.go:211-286: double denom, clamp, 0 -> 1 */
-                    double denom = sqrt((double)rn0) * sqrt((double)ldsn[t]);
-                    if (denom == 0.0) dist = 1.0f;
-                    else {
-                        double sim = (double)acc0[t] / denom;
-                        sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-                        dist = (float)(1.0 - sim);
-                    }
-                } else dist = acc0[t];
-                dists_out[ob + row0] = pass0 ? dist : FLT_MAX;
-            }
-            if (has1 && row1 < rows) {
-                float dist;
-                if (METRIC == KM_IP) dist = -acc1[t];
-                else if (METRIC == KM_COS) {
-                    double denom = sqrt((double)rn1) * sqrt((double)ldsn[t]);
-                    if (denom == 0.0) dist = 1.0f;
-                    else {
-                        double sim = (double)acc1[t] / denom;
-                        sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-                        dist = (float)(1.0 - sim);
-                    }
-                } else dist = acc1[t];
-                dists_out[ob + row1] = pass1 ? dist : FLT_MAX;
-            }
-        }
+        store_group_pair<QT, METRIC == KM_COS>(
+            jobs, jv, lane, g0, g1, has1, acc0, acc1, rn0, rn1, ldsn,
+            filter_bitset, dists_out, [](float acc, float rn, float qn) {
+                return finish_f32<METRIC>(acc, rn, qn);
+            });
     }
 }
 
@@ -299,36 +150,6 @@ __global__ __launch_bounds__(256) void scan_kernel(
     throw std::logic_error(std::string(launcher) + ": no kernel for scan " +
                            scan_kind_name(v.kind) + " qt=" +
                            std::to_string(v.qt));
-}
-
-template <int METRIC>
-static void launch_scan_qt(int qt, const float* packed, const float* queries,
-                           const float* qnorms, int dpad, const ScanJobs& jb,
-                           float* dists_out, hipStream_t stream,
-                           const uint32_t* filter_bitset) {
-    const dim3 grid(jb.njobs), block(256);
-#define ARGS packed, queries, qnorms, dpad, jb.databaseg, jb.gstart, \
-    jb.gcount, jb.rows, jb.nq, jb.qbase, jb.qslot_query, jb.qslot_outbase, \
-    jb.slot_base, filter_bitset, dists_out
-    switch (qt) { /* launch_scan admits only these four widths */
-    case 8:
-        hipLaunchKernelGGL((scan_kernel<METRIC, 8, 2>), grid, block,
-                           (8 * dpad + 8) * sizeof(float), stream, ARGS);
-        break;
-    case 4:
-        hipLaunchKernelGGL((scan_kernel<METRIC, 4, 2>), grid, block,
-                           (4 * dpad + 4) * sizeof(float), stream, ARGS);
-        break;
-    case 2:
-        hipLaunchKernelGGL((scan_kernel<METRIC, 2, 2>), grid, block,
-                           (2 * dpad + 2) * sizeof(float), stream, ARGS);
-        break;
-    default:
-        hipLaunchKernelGGL((scan_kernel<METRIC, 1, 2>), grid, block,
-                           (1 * dpad + 1) * sizeof(float), stream, ARGS);
-        break;
-    }
-#undef ARGS
 }
 
 void launch_scan(int metric, ScanVariant v, const float* packed,
@@ -347,12 +168,22 @@ void launch_scan(int metric, ScanVariant v, const float* packed,
                            filter_bitset);
         return;
     }
-    switch (metric) {
-    case KM_L2SQ: launch_scan_qt<KM_L2SQ>(qt, packed, queries, qnorms, dpad, jb, dists_out, stream, filter_bitset); break;
-    case KM_IP:   launch_scan_qt<KM_IP>(qt, packed, queries, qnorms, dpad, jb, dists_out, stream, filter_bitset); break;
-    case KM_COS:  launch_scan_qt<KM_COS>(qt, packed, queries, qnorms, dpad, jb, dists_out, stream, filter_bitset); break;
-    default:      launch_scan_qt<KM_L1>(qt, packed, queries, qnorms, dpad, jb, dists_out, stream, filter_bitset); break;
-    }
+    with_metric(metric, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        const dim3 grid(jb.njobs), block(256);
+        const size_t shmem = (size_t)(qt * dpad + qt) * sizeof(float);
+        const auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, shmem, stream, packed,
+                               queries, qnorms, dpad, jb, filter_bitset,
+                               dists_out);
+        };
+        switch (qt) { /* only the four widths admitted above */
+        case 8:  launch(scan_kernel<M, 8>); break;
+        case 4:  launch(scan_kernel<M, 4>); break;
+        case 2:  launch(scan_kernel<M, 2>); break;
+        default: launch(scan_kernel<M, 1>); break;
+        }
+    });
 }
 
 /* ------------------------------ top-k ------------------------------------
@@ -845,18 +676,11 @@ void launch_qnorms_h(bool bf, const uint16_t* q, int nq, int dpad, float* out,
 }
 
 /* half-storage list scan: dwordx4 = 8 halves/lane per step, decoded to
- * f32, same job/filter/output semantics as the other scans. QT=8, GP=2. */
+ * f32, same job/filter/output semantics as the other scans. QT=8. */
 template <int METRIC, bool BF>
 __global__ __launch_bounds__(256) void scan_h_kernel(
     const uint16_t* __restrict__ packed, const uint16_t* __restrict__ queries_h,
-    const float* __restrict__ qnorms, int dpad,
-    const int64_t* __restrict__ j_databaseg,
-    const int32_t* __restrict__ j_gstart, const int32_t* __restrict__ j_gcount,
-    const int32_t* __restrict__ j_rows, const int32_t* __restrict__ j_nq,
-    const int32_t* __restrict__ j_qbase,
-    const int32_t* __restrict__ qslot_query,
-    const int64_t* __restrict__ qslot_outbase,
-    const int64_t* __restrict__ j_slot_base,
+    const float* __restrict__ qnorms, int dpad, const ScanJobs jobs,
     const uint32_t* __restrict__ filter_bitset,
     float* __restrict__ dists_out) {
     constexpr int QT = 8;
@@ -864,47 +688,23 @@ __global__ __launch_bounds__(256) void scan_h_kernel(
     uint16_t* ldsq = (uint16_t*)ldsf;           /* [QT][dpad] halves */
     float* ldsn = (float*)(ldsq + QT * dpad);
 
-    int j;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        j = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-        if (j >= nwg) j = bid;
-    }
-    const int nq = j_nq[j];
-    const int qbase = j_qbase[j];
-    for (int t = 0; t < QT; ++t) {
-        if (t < nq) {
-            const int q = qslot_query[qbase + t];
-            const uint16_t* src = queries_h + (int64_t)q * dpad;
-            for (int e = threadIdx.x; e < dpad; e += blockDim.x)
-                ldsq[t * dpad + e] = src[e];
-            if (METRIC == KM_COS && threadIdx.x == 0) ldsn[t] = qnorms[q];
-        } else {
-            for (int e = threadIdx.x; e < dpad; e += blockDim.x)
-                ldsq[t * dpad + e] = 0;
-            if (METRIC == KM_COS && threadIdx.x == 0) ldsn[t] = 0.f;
-        }
-    }
-    __syncthreads();
+    const JobView jv = load_job(jobs);
+    stage_query_tile<QT, METRIC == KM_COS>(jv, jobs.qslot_query, queries_h,
+                                           qnorms, dpad, ldsq, ldsn);
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gstart = j_gstart[j], gcount = j_gcount[j];
-    const int rows = j_rows[j];
-    const int64_t baseg = j_databaseg[j];
+    const int gend = jv.gstart + jv.gcount;
     const int d8 = dpad >> 3;
 
 #define MOANN_H8(w, out0, out1)                                                  {                                                                                const float va = BF ? moann_bf2f((uint16_t)((w) & 0xFFFF))                                       : moann_h2f((uint16_t)((w) & 0xFFFF));                   const float vb = BF ? moann_bf2f((uint16_t)((w) >> 16))                                          : moann_h2f((uint16_t)((w) >> 16));                      out0 = va;                                                                   out1 = vb;                                                               }
 
-    for (int gp = gstart + 2 * wave; gp < gstart + gcount; gp += 8) {
-        const int g0 = gp;
-        const bool has1 = (gp + 1) < (gstart + gcount);
-        const int g1 = has1 ? gp + 1 : gp;
+    for (int g0 = jv.gstart + 2 * wave; g0 < gend; g0 += 8) {
+        const bool has1 = (g0 + 1) < gend;
+        const int g1 = has1 ? g0 + 1 : g0;
         const uint4* __restrict__ d0 =
-            (const uint4*)(packed + (baseg + g0) * (int64_t)64 * dpad) + lane;
+            (const uint4*)(packed + (jv.baseg + g0) * (int64_t)64 * dpad) + lane;
         const uint4* __restrict__ d1 =
-            (const uint4*)(packed + (baseg + g1) * (int64_t)64 * dpad) + lane;
+            (const uint4*)(packed + (jv.baseg + g1) * (int64_t)64 * dpad) + lane;
 
         float acc0[QT], acc1[QT];
 #pragma unroll
@@ -953,76 +753,12 @@ __global__ __launch_bounds__(256) void scan_h_kernel(
         }
 #undef MOANN_H8
 
-        const int row0 = g0 * 64 + lane;
-        const int row1 = g1 * 64 + lane;
-        bool pass0 = true, pass1 = true;
-        if (filter_bitset) {
-            const int64_t sb = j_slot_base[j];
-            if (row0 < rows) {
-                const int64_t gs = sb + row0;
-                pass0 = (filter_bitset[gs >> 5] >> (gs & 31)) & 1u;
-            }
-            if (has1 && row1 < rows) {
-                const int64_t gs = sb + row1;
-                pass1 = (filter_bitset[gs >> 5] >> (gs & 31)) & 1u;
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            if (t >= nq) break;
-            const int64_t ob = qslot_outbase[qbase + t];
-            if (row0 < rows) {
-                float dist;
-                if (METRIC == KM_IP) dist = -acc0[t];
-                else if (METRIC == KM_COS) {
-                    const double denom =
-                        sqrt((double)rn0) * sqrt((double)ldsn[t]);
-                    if (denom == 0.0) dist = 1.0f;
-                    else {
-                        double sim = (double)acc0[t] / denom;
-                        sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-                        dist = (float)(1.0 - sim);
-                    }
-                } else dist = acc0[t];
-                dists_out[ob + row0] = pass0 ? dist : FLT_MAX;
-            }
-            if (has1 && row1 < rows) {
-                float dist;
-                if (METRIC == KM_IP) dist = -acc1[t];
-                else if (METRIC == KM_COS) {
-                    const double denom =
-                        sqrt((double)rn1) * sqrt((double)ldsn[t]);
-                    if (denom == 0.0) dist = 1.0f;
-                    else {
-                        double sim = (double)acc1[t] / denom;
-                        sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-                        dist = (float)(1.0 - sim);
-                    }
-                } else dist = acc1[t];
-                dists_out[ob + row1] = pass1 ? dist : FLT_MAX;
-            }
-        }
+        store_group_pair<QT, METRIC == KM_COS>(
+            jobs, jv, lane, g0, g1, has1, acc0, acc1, rn0, rn1, ldsn,
+            filter_bitset, dists_out, [](float acc, float rn, float qn) {
+                return finish_f32<METRIC>(acc, rn, qn);
+            });
     }
-}
-
-template <int METRIC>
-static void launch_scan_h_m(bool bf, const uint16_t* packed,
-                            const uint16_t* queries_h, const float* qnorms,
-                            int dpad, const ScanJobs& jb, float* dists_out,
-                            hipStream_t stream,
-                            const uint32_t* filter_bitset) {
-    const dim3 grid(jb.njobs), block(256);
-    const size_t shmem = 8 * dpad * 2 + 8 * 4 + 16;
-#define HFARGS packed, queries_h, qnorms, dpad, jb.databaseg, jb.gstart, \
-    jb.gcount, jb.rows, jb.nq, jb.qbase, jb.qslot_query, jb.qslot_outbase, \
-    jb.slot_base, filter_bitset, dists_out
-    if (bf)
-        hipLaunchKernelGGL((scan_h_kernel<METRIC, true>), grid, block, shmem,
-                           stream, HFARGS);
-    else
-        hipLaunchKernelGGL((scan_h_kernel<METRIC, false>), grid, block,
-                           shmem, stream, HFARGS);
-#undef HFARGS
 }
 
 void launch_scan_h(int metric, ScanVariant v, bool bf,
@@ -1032,12 +768,17 @@ void launch_scan_h(int metric, ScanVariant v, bool bf,
                    const uint32_t* filter_bitset) {
     if (v.kind != ScanKind::HALF || v.qt != 8) bad_variant("launch_scan_h", v);
     if (!jb.njobs) return;
-    switch (metric) {
-    case KM_L2SQ: launch_scan_h_m<KM_L2SQ>(bf, packed, queries_h, qnorms, dpad, jb, dists_out, stream, filter_bitset); break;
-    case KM_IP:   launch_scan_h_m<KM_IP>(bf, packed, queries_h, qnorms, dpad, jb, dists_out, stream, filter_bitset); break;
-    case KM_COS:  launch_scan_h_m<KM_COS>(bf, packed, queries_h, qnorms, dpad, jb, dists_out, stream, filter_bitset); break;
-    default:      launch_scan_h_m<KM_L1>(bf, packed, queries_h, qnorms, dpad, jb, dists_out, stream, filter_bitset); break;
-    }
+    with_metric(metric, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        const dim3 grid(jb.njobs), block(256);
+        const size_t shmem = 8 * dpad * 2 + 8 * 4 + 16;
+        const auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, shmem, stream, packed,
+                               queries_h, qnorms, dpad, jb, filter_bitset,
+                               dists_out);
+        };
+        bf ? launch(scan_h_kernel<M, true>) : launch(scan_h_kernel<M, false>);
+    });
 }
 
 /* ---------------- exact f32 refine (two-stage scan) ---------------------
@@ -1100,18 +841,12 @@ __global__ __launch_bounds__(256) void refine_kernel(
             acc += __shfl_down(acc, off, 64);
             if (METRIC == KM_COS) rn += __shfl_down(rn, off, 64);
         }
-        if (lane == 0) {
+        if (lane == 0) { /* qnorms is null unless cos */
             float dist;
             if (METRIC == KM_IP) dist = -acc;
-            else if (METRIC == KM_COS) {
-                const double denom = sqrt((double)rn) * sqrt((double)qnorms[q]);
-                if (denom == 0.0) dist = 1.0f;
-                else {
-                    double sim = (double)acc / denom;
-                    sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-                    dist = (float)(1.0 - sim);
-                }
-            } else dist = acc;
+            else if (METRIC == KM_COS)
+                dist = mo_cos_distance(acc, rn, qnorms[q]);
+            else dist = acc;
             refined[idx] = dist;
         }
     }
@@ -1125,15 +860,12 @@ void launch_refine(int metric, const float* rows_f32, const float* queries,
                    hipStream_t stream) {
     if (!nq) return;
     const size_t shmem = (size_t)dpad * 4;
-#define RARGS rows_f32, queries, qnorms, dim, dpad, R, rsel_slots, \
-    rsel_dists, probe_lists, probe_offs, list_slot_base, nprobe, refined
-    switch (metric) {
-    case KM_L2SQ: hipLaunchKernelGGL(refine_kernel<KM_L2SQ>, dim3(nq), dim3(256), shmem, stream, RARGS); break;
-    case KM_IP:   hipLaunchKernelGGL(refine_kernel<KM_IP>, dim3(nq), dim3(256), shmem, stream, RARGS); break;
-    case KM_COS:  hipLaunchKernelGGL(refine_kernel<KM_COS>, dim3(nq), dim3(256), shmem, stream, RARGS); break;
-    default:      hipLaunchKernelGGL(refine_kernel<KM_L1>, dim3(nq), dim3(256), shmem, stream, RARGS); break;
-    }
-#undef RARGS
+    with_metric(metric, [&](auto m) {
+        hipLaunchKernelGGL(refine_kernel<decltype(m)::value>, dim3(nq),
+                           dim3(256), shmem, stream, rows_f32, queries, qnorms,
+                           dim, dpad, R, rsel_slots, rsel_dists, probe_lists,
+                           probe_offs, list_slot_base, nprobe, refined);
+    });
 }
 
 /* final-selection composition: sel2 indexes into the refine set; map back
@@ -1172,14 +904,7 @@ template <int METRIC, bool UNSIGNED>
 __global__ __launch_bounds__(256) void scan_i8_kernel(
     const uint8_t* __restrict__ packed, const uint8_t* __restrict__ queries_q,
     const int32_t* __restrict__ qnorms_i /* [nq] sum sq, cos only */,
-    int dpad,
-    const int64_t* __restrict__ j_databaseg,
-    const int32_t* __restrict__ j_gstart, const int32_t* __restrict__ j_gcount,
-    const int32_t* __restrict__ j_rows, const int32_t* __restrict__ j_nq,
-    const int32_t* __restrict__ j_qbase,
-    const int32_t* __restrict__ qslot_query,
-    const int64_t* __restrict__ qslot_outbase,
-    const int64_t* __restrict__ j_slot_base,
+    int dpad, const ScanJobs jobs,
     const uint32_t* __restrict__ filter_bitset,
     float* __restrict__ dists_out) {
     constexpr int QT = 8;
@@ -1187,49 +912,25 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(
     uint8_t* ldsq = (uint8_t*)ldsf;            /* [QT][dpad] bytes */
     int32_t* ldsn = (int32_t*)(ldsq + QT * dpad);
 
-    int j;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        j = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-        if (j >= nwg) j = bid;
-    }
-    const int nq = j_nq[j];
-    const int qbase = j_qbase[j];
-    for (int t = 0; t < QT; ++t) {
-        if (t < nq) {
-            const int q = qslot_query[qbase + t];
-            const uint8_t* src = queries_q + (int64_t)q * dpad;
-            for (int e = threadIdx.x; e < dpad; e += blockDim.x)
-                ldsq[t * dpad + e] = src[e];
-            if (METRIC == KM_COS && threadIdx.x == 0) ldsn[t] = qnorms_i[q];
-        } else {
-            for (int e = threadIdx.x; e < dpad; e += blockDim.x)
-                ldsq[t * dpad + e] = 0;
-            if (METRIC == KM_COS && threadIdx.x == 0) ldsn[t] = 0;
-        }
-    }
-    __syncthreads();
+    const JobView jv = load_job(jobs);
+    stage_query_tile<QT, METRIC == KM_COS>(jv, jobs.qslot_query, queries_q,
+                                           qnorms_i, dpad, ldsq, ldsn);
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gstart = j_gstart[j], gcount = j_gcount[j];
-    const int rows = j_rows[j];
-    const int64_t baseg = j_databaseg[j];
+    const int gend = jv.gstart + jv.gcount;
     const int d4 = dpad >> 2;
 
     const auto sx = [](uint8_t b) -> int {
         return UNSIGNED ? (int)b : (int)(int8_t)b;
     };
 
-    for (int gp = gstart + 2 * wave; gp < gstart + gcount; gp += 8) {
-        const int g0 = gp;
-        const bool has1 = (gp + 1) < (gstart + gcount);
-        const int g1 = has1 ? gp + 1 : gp;
+    for (int g0 = jv.gstart + 2 * wave; g0 < gend; g0 += 8) {
+        const bool has1 = (g0 + 1) < gend;
+        const int g1 = has1 ? g0 + 1 : g0;
         const uchar4* __restrict__ d0 =
-            (const uchar4*)(packed + (baseg + g0) * (int64_t)64 * dpad) + lane;
+            (const uchar4*)(packed + (jv.baseg + g0) * (int64_t)64 * dpad) + lane;
         const uchar4* __restrict__ d1 =
-            (const uchar4*)(packed + (baseg + g1) * (int64_t)64 * dpad) + lane;
+            (const uchar4*)(packed + (jv.baseg + g1) * (int64_t)64 * dpad) + lane;
         int32_t acc0[QT], acc1[QT];
 #pragma unroll
         for (int t = 0; t < QT; ++t) acc0[t] = acc1[t] = 0;
@@ -1274,56 +975,11 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(
                 }
             }
         }
-        const int row0 = g0 * 64 + lane;
-        const int row1 = g1 * 64 + lane;
-        bool pass0 = true, pass1 = true;
-        if (filter_bitset) {
-            const int64_t sb = j_slot_base[j];
-            if (row0 < rows) {
-                const int64_t gs = sb + row0;
-                pass0 = (filter_bitset[gs >> 5] >> (gs & 31)) & 1u;
-            }
-            if (has1 && row1 < rows) {
-                const int64_t gs = sb + row1;
-                pass1 = (filter_bitset[gs >> 5] >> (gs & 31)) & 1u;
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            if (t >= nq) break;
-            const int64_t ob = qslot_outbase[qbase + t];
-            if (row0 < rows) {
-                float dist;
-                if (METRIC == KM_IP) dist = (float)(-(int64_t)acc0[t]);
-                else if (METRIC == KM_COS) {
-                    /* distance_func_narrow.go:444-449: int sums -> double */
-                    const double denom =
-                        sqrt((double)rn0) * sqrt((double)ldsn[t]);
-                    if (denom == 0.0) dist = 1.0f;
-                    else {
-                        double sim = (double)acc0[t] / denom;
-                        sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-                        dist = (float)(1.0 - sim);
-                    }
-                } else dist = (float)acc0[t];
-                dists_out[ob + row0] = pass0 ? dist : FLT_MAX;
-            }
-            if (has1 && row1 < rows) {
-                float dist;
-                if (METRIC == KM_IP) dist = (float)(-(int64_t)acc1[t]);
-                else if (METRIC == KM_COS) {
-                    const double denom =
-                        sqrt((double)rn1) * sqrt((double)ldsn[t]);
-                    if (denom == 0.0) dist = 1.0f;
-                    else {
-                        double sim = (double)acc1[t] / denom;
-                        sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-                        dist = (float)(1.0 - sim);
-                    }
-                } else dist = (float)acc1[t];
-                dists_out[ob + row1] = pass1 ? dist : FLT_MAX;
-            }
-        }
+        store_group_pair<QT, METRIC == KM_COS>(
+            jobs, jv, lane, g0, g1, has1, acc0, acc1, rn0, rn1, ldsn,
+            filter_bitset, dists_out, [](int32_t acc, int32_t rn, int32_t qn) {
+                return finish_i32<METRIC, false>(acc, rn, qn);
+            });
     }
 }
 
@@ -1345,14 +1001,7 @@ __global__ __launch_bounds__(256) void scan_i8_dot_kernel(
     const uint8_t* __restrict__ packed, const uint8_t* __restrict__ queries_q,
     const int32_t* __restrict__ qnorms_i, /* [nq] sum sq (l2/cos) */
     const int32_t* __restrict__ rownorms, /* [ngroups*64] sum sq (l2/cos) */
-    int dpad,
-    const int64_t* __restrict__ j_databaseg,
-    const int32_t* __restrict__ j_gstart, const int32_t* __restrict__ j_gcount,
-    const int32_t* __restrict__ j_rows, const int32_t* __restrict__ j_nq,
-    const int32_t* __restrict__ j_qbase,
-    const int32_t* __restrict__ qslot_query,
-    const int64_t* __restrict__ qslot_outbase,
-    const int64_t* __restrict__ j_slot_base,
+    int dpad, const ScanJobs jobs,
     const uint32_t* __restrict__ filter_bitset,
     float* __restrict__ dists_out) {
     constexpr bool NEED_N = METRIC == KM_L2SQ || METRIC == KM_COS;
@@ -1360,45 +1009,21 @@ __global__ __launch_bounds__(256) void scan_i8_dot_kernel(
     uint8_t* ldsq = (uint8_t*)ldsf;            /* [QT][dpad] bytes */
     int32_t* ldsn = (int32_t*)(ldsq + QT * dpad);
 
-    int j;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int q8 = nwg >> 3, r8 = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        j = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-        if (j >= nwg) j = bid;
-    }
-    const int nq = j_nq[j];
-    const int qbase = j_qbase[j];
-    for (int t = 0; t < QT; ++t) {
-        if (t < nq) {
-            const int q = qslot_query[qbase + t];
-            const uint8_t* src = queries_q + (int64_t)q * dpad;
-            for (int e = threadIdx.x; e < dpad; e += blockDim.x)
-                ldsq[t * dpad + e] = src[e];
-            if (NEED_N && threadIdx.x == 0) ldsn[t] = qnorms_i[q];
-        } else {
-            for (int e = threadIdx.x; e < dpad; e += blockDim.x)
-                ldsq[t * dpad + e] = 0;
-            if (NEED_N && threadIdx.x == 0) ldsn[t] = 0;
-        }
-    }
-    __syncthreads();
+    const JobView jv = load_job(jobs);
+    stage_query_tile<QT, NEED_N>(jv, jobs.qslot_query, queries_q, qnorms_i,
+                                 dpad, ldsq, ldsn);
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int gstart = j_gstart[j], gcount = j_gcount[j];
-    const int rows = j_rows[j];
-    const int64_t baseg = j_databaseg[j];
+    const int gend = jv.gstart + jv.gcount;
     const int d16 = dpad >> 4;
 
-    for (int gp = gstart + 2 * wave; gp < gstart + gcount; gp += 8) {
-        const int g0 = gp;
-        const bool has1 = (gp + 1) < (gstart + gcount);
-        const int g1 = has1 ? gp + 1 : gp;
+    for (int g0 = jv.gstart + 2 * wave; g0 < gend; g0 += 8) {
+        const bool has1 = (g0 + 1) < gend;
+        const int g1 = has1 ? g0 + 1 : g0;
         const uint4* __restrict__ d0 =
-            (const uint4*)(packed + (baseg + g0) * (int64_t)64 * dpad) + lane;
+            (const uint4*)(packed + (jv.baseg + g0) * (int64_t)64 * dpad) + lane;
         const uint4* __restrict__ d1 =
-            (const uint4*)(packed + (baseg + g1) * (int64_t)64 * dpad) + lane;
+            (const uint4*)(packed + (jv.baseg + g1) * (int64_t)64 * dpad) + lane;
 
         int32_t acc0[QT], acc1[QT];
 #pragma unroll
@@ -1453,61 +1078,13 @@ __global__ __launch_bounds__(256) void scan_i8_dot_kernel(
             }
         }
 
-        const int row0 = g0 * 64 + lane;
-        const int row1 = g1 * 64 + lane;
-        const int32_t rn0 = NEED_N ? rownorms[(baseg + g0) * 64 + lane] : 0;
-        const int32_t rn1 = NEED_N ? rownorms[(baseg + g1) * 64 + lane] : 0;
-        bool pass0 = true, pass1 = true;
-        if (filter_bitset) {
-            const int64_t sb = j_slot_base[j];
-            if (row0 < rows) {
-                const int64_t gs = sb + row0;
-                pass0 = (filter_bitset[gs >> 5] >> (gs & 31)) & 1u;
-            }
-            if (has1 && row1 < rows) {
-                const int64_t gs = sb + row1;
-                pass1 = (filter_bitset[gs >> 5] >> (gs & 31)) & 1u;
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            if (t >= nq) break;
-            const int64_t ob = qslot_outbase[qbase + t];
-            if (row0 < rows) {
-                float dist;
-                if (METRIC == KM_IP) dist = (float)(-(int64_t)acc0[t]);
-                else if (METRIC == KM_COS) {
-                    const double denom =
-                        sqrt((double)rn0) * sqrt((double)ldsn[t]);
-                    if (denom == 0.0) dist = 1.0f;
-                    else {
-                        double sim = (double)acc0[t] / denom;
-                        sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-                        dist = (float)(1.0 - sim);
-                    }
-                } else if (METRIC == KM_L2SQ)
-                    dist = (float)(rn0 + ldsn[t] - 2 * acc0[t]);
-                else dist = (float)acc0[t]; /* L1 */
-                dists_out[ob + row0] = pass0 ? dist : FLT_MAX;
-            }
-            if (has1 && row1 < rows) {
-                float dist;
-                if (METRIC == KM_IP) dist = (float)(-(int64_t)acc1[t]);
-                else if (METRIC == KM_COS) {
-                    const double denom =
-                        sqrt((double)rn1) * sqrt((double)ldsn[t]);
-                    if (denom == 0.0) dist = 1.0f;
-                    else {
-                        double sim = (double)acc1[t] / denom;
-                        sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-                        dist = (float)(1.0 - sim);
-                    }
-                } else if (METRIC == KM_L2SQ)
-                    dist = (float)(rn1 + ldsn[t] - 2 * acc1[t]);
-                else dist = (float)acc1[t];
-                dists_out[ob + row1] = pass1 ? dist : FLT_MAX;
-            }
-        }
+        const int32_t rn0 = NEED_N ? rownorms[(jv.baseg + g0) * 64 + lane] : 0;
+        const int32_t rn1 = NEED_N ? rownorms[(jv.baseg + g1) * 64 + lane] : 0;
+        store_group_pair<QT, NEED_N>(
+            jobs, jv, lane, g0, g1, has1, acc0, acc1, rn0, rn1, ldsn,
+            filter_bitset, dists_out, [](int32_t acc, int32_t rn, int32_t qn) {
+                return finish_i32<METRIC, true>(acc, rn, qn);
+            });
     }
 }
 
@@ -1596,48 +1173,6 @@ void launch_rownorms_i8(bool uns, const uint8_t* packed, int64_t ngroups,
                            packed, ngroups, dpad, out);
 }
 
-template <int METRIC>
-static void launch_scan_i8_m(bool uns, const uint8_t* packed,
-                             const uint8_t* queries_q, const int32_t* qnorms,
-                             const int32_t* rownorms, int dpad,
-                             const ScanJobs& jb, float* dists_out,
-                             hipStream_t stream,
-                             const uint32_t* filter_bitset, ScanVariant v) {
-    const dim3 grid(jb.njobs), block(256);
-    const int qt = v.qt;
-    const size_t shmem = (size_t)qt * dpad + (size_t)qt * 4 + 16;
-    /* dot form (16-dim-aligned rows + row norms) or the uchar4 kernel */
-    const bool dot = v.kind == ScanKind::BYTE_DOT;
-#define I8ARGS packed, queries_q, qnorms, dpad, jb.databaseg, jb.gstart, \
-    jb.gcount, jb.rows, jb.nq, jb.qbase, jb.qslot_query, jb.qslot_outbase, \
-    jb.slot_base, filter_bitset, dists_out
-#define I8DARGS packed, queries_q, qnorms, rownorms, dpad, jb.databaseg, \
-    jb.gstart, jb.gcount, jb.rows, jb.nq, jb.qbase, jb.qslot_query, \
-    jb.qslot_outbase, jb.slot_base, filter_bitset, dists_out
-    if (dot && qt == 16) {
-        if (uns)
-            hipLaunchKernelGGL((scan_i8_dot_kernel<METRIC, true, 16>), grid,
-                               block, shmem, stream, I8DARGS);
-        else
-            hipLaunchKernelGGL((scan_i8_dot_kernel<METRIC, false, 16>), grid,
-                               block, shmem, stream, I8DARGS);
-    } else if (dot) {
-        if (uns)
-            hipLaunchKernelGGL((scan_i8_dot_kernel<METRIC, true, 8>), grid,
-                               block, shmem, stream, I8DARGS);
-        else
-            hipLaunchKernelGGL((scan_i8_dot_kernel<METRIC, false, 8>), grid,
-                               block, shmem, stream, I8DARGS);
-    } else if (uns)
-        hipLaunchKernelGGL((scan_i8_kernel<METRIC, true>), grid, block, shmem,
-                           stream, I8ARGS);
-    else
-        hipLaunchKernelGGL((scan_i8_kernel<METRIC, false>), grid, block,
-                           shmem, stream, I8ARGS);
-#undef I8ARGS
-#undef I8DARGS
-}
-
 void launch_scan_i8(int metric, ScanVariant v, bool uns,
                     const uint8_t* packed, const uint8_t* queries_q,
                     const int32_t* qnorms, const int32_t* rownorms, int dpad,
@@ -1651,12 +1186,31 @@ void launch_scan_i8(int metric, ScanVariant v, bool uns,
     if (dot_ok && !rownorms)
         throw std::logic_error("launch_scan_i8: BYTE_DOT without row norms");
     if (!jb.njobs) return;
-    switch (metric) {
-    case KM_L2SQ: launch_scan_i8_m<KM_L2SQ>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, v); break;
-    case KM_IP:   launch_scan_i8_m<KM_IP>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, v); break;
-    case KM_COS:  launch_scan_i8_m<KM_COS>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, v); break;
-    default:      launch_scan_i8_m<KM_L1>(uns, packed, queries_q, qnorms, rownorms, dpad, jb, dists_out, stream, filter_bitset, v); break;
-    }
+    with_metric(metric, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        const dim3 grid(jb.njobs), block(256);
+        const int qt = v.qt;
+        const size_t shmem = (size_t)qt * dpad + (size_t)qt * 4 + 16;
+        /* dot form (16-dim-aligned rows + row norms) or the uchar4 kernel */
+        const auto dot = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, shmem, stream, packed,
+                               queries_q, qnorms, rownorms, dpad, jb,
+                               filter_bitset, dists_out);
+        };
+        const auto u4 = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, shmem, stream, packed,
+                               queries_q, qnorms, dpad, jb, filter_bitset,
+                               dists_out);
+        };
+        if (dot_ok && qt == 16)
+            uns ? dot(scan_i8_dot_kernel<M, true, 16>)
+                : dot(scan_i8_dot_kernel<M, false, 16>);
+        else if (dot_ok)
+            uns ? dot(scan_i8_dot_kernel<M, true, 8>)
+                : dot(scan_i8_dot_kernel<M, false, 8>);
+        else
+            uns ? u4(scan_i8_kernel<M, true>) : u4(scan_i8_kernel<M, false>);
+    });
 }
 
 /* quantize f32 rows -> int8/uint8 with the reference's exact semantics:
@@ -1778,18 +1332,7 @@ __global__ __launch_bounds__(256) void pairwise_kernel(
         if (METRIC == KM_COS) nrm += __shfl_down(nrm, w, 64);
     }
     if (lane) return;
-    float dist;
-    if (METRIC == KM_IP) dist = -acc;
-    else if (METRIC == KM_COS) {
-        const double denom = sqrt((double)nrm) * sqrt((double)qnorm);
-        if (denom == 0.0) dist = 1.0f;
-        else {
-            double sim = (double)acc / denom;
-            sim = sim > 1.0 ? 1.0 : (sim < -1.0 ? -1.0 : sim);
-            dist = (float)(1.0 - sim);
-        }
-    } else dist = acc;
-    out[r] = dist;
+    out[r] = finish_f32<METRIC>(acc, nrm, qnorm);
 }
 
 void launch_pairwise(int metric, const float* rows, const float* query,
@@ -1798,28 +1341,11 @@ void launch_pairwise(int metric, const float* rows, const float* query,
     if (!n) return;
     const int wpb = 4;
     const int64_t grid = (n + wpb - 1) / wpb;
-    switch (metric) {
-    case KM_L2SQ:
-        hipLaunchKernelGGL((pairwise_kernel<KM_L2SQ>), dim3((uint32_t)grid),
-                           dim3(wpb * 64), 0, stream, rows, query, qnorm, n,
-                           dim, out);
-        break;
-    case KM_IP:
-        hipLaunchKernelGGL((pairwise_kernel<KM_IP>), dim3((uint32_t)grid),
-                           dim3(wpb * 64), 0, stream, rows, query, qnorm, n,
-                           dim, out);
-        break;
-    case KM_COS:
-        hipLaunchKernelGGL((pairwise_kernel<KM_COS>), dim3((uint32_t)grid),
-                           dim3(wpb * 64), 0, stream, rows, query, qnorm, n,
-                           dim, out);
-        break;
-    default:
-        hipLaunchKernelGGL((pairwise_kernel<KM_L1>), dim3((uint32_t)grid),
-                           dim3(wpb * 64), 0, stream, rows, query, qnorm, n,
-                           dim, out);
-        break;
-    }
+    with_metric(metric, [&](auto m) {
+        hipLaunchKernelGGL((pairwise_kernel<decltype(m)::value>),
+                           dim3((uint32_t)grid), dim3(wpb * 64), 0, stream,
+                           rows, query, qnorm, n, dim, out);
+    });
 }
 
 /* --------------------------- query norms ---------------------------------

@@ -40,7 +40,7 @@ inline int metric_kind(distance_type_t m) {
 /* ------------------------------ scan variant ---------------------------- */
 
 enum class ScanKind {
-    F32,        /* scan_kernel<metric, qt, 2>, qt in {8,4,2,1}               */
+    F32,        /* scan_kernel<metric, qt>, qt in {8,4,2,1}                  */
     F32_ASM768, /* scan_asm768.hip: L2SQ, dpad 768, qt 16                    */
     HALF,       /* scan_h_kernel (f16/bf16 storage), qt 8                    */
     BYTE_DOT,   /* scan_i8_dot_kernel, qt 16 or 8                            */

@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "moann_internal.h"
+#include "moann_scan_device.h" /* slot_passes */
 
 namespace moann {
 
@@ -219,8 +220,7 @@ __global__ __launch_bounds__(1024) void pq_scan_q_kernel(
             if (row < rows) {
                 const int64_t gs = sbase + row;
                 const bool pass =
-                    !filter_bitset ||
-                    ((filter_bitset[gs >> 5] >> (gs & 31)) & 1u);
+                    !filter_bitset || slot_passes(filter_bitset, gs);
                 dists_out[ob + row] =
                     pass ? acc + row_b[gs] + dconst : FLT_MAX;
             }

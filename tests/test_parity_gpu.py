@@ -725,6 +725,92 @@ def test_half_storage_odd_dim_and_saveload(tmp_path):
     ix2.close()
 
 
+_EPILOGUE_DATA = {}
+
+
+def _epilogue_data(d):
+    """Seeded inputs of test_scan_epilogue_cells, built once per dim."""
+    if d not in _EPILOGUE_DATA:
+        rng = np.random.Generator(np.random.PCG64(1700 + d))
+        n, nlist, nq = 4000, 16, 12
+        vecs = rng.standard_normal((n, d), dtype=np.float32)
+        cents = vecs[rng.choice(n, nlist, replace=False)].copy()
+        assign = ((vecs[:, None, :].astype(np.float64) -
+                   cents[None].astype(np.float64)) ** 2).sum(-1).argmin(1)
+        ids64 = rng.permutation(n).astype(np.int64) * 3 + 11
+        queries = rng.standard_normal((nq, d), dtype=np.float32)
+        allowed = ids64[rng.random(n) < 0.2]
+        _EPILOGUE_DATA[d] = (vecs, cents, assign, ids64, queries, allowed)
+    return _EPILOGUE_DATA[d]
+
+
+@pytest.mark.parametrize("qtype,d,metric,filtered", [
+    ("f16", 96, "l2sq", True), ("bf16", 96, "l2sq", True),
+    ("int8", 96, "l2sq", True), ("int8", 100, "l2sq", True),
+    ("f16", 96, "cos", True), ("int8", 96, "cos", True),
+    ("uint8", 96, "ip", False), ("uint8", 96, "cos", False),
+    ("uint8", 96, "l1", False), ("uint8", 100, "ip", False),
+    ("uint8", 100, "cos", False), ("uint8", 100, "l1", False),
+    ("bf16", 96, "l1", False)])
+def test_scan_epilogue_cells(qtype, d, metric, filtered):
+    """The filter test, distance finish and store that every list-scan
+    kernel shares, per storage type x metric x filter cell the other tests
+    leave out: membership-filtered half and byte scans (d=96: dpad % 16 == 0,
+    dot form; d=100: uchar4 form), uint8 under ip/cos/l1 in both byte forms,
+    bf16 under l1. nq=12 is one partial tile at width 8 and at width 16;
+    random list sizes give odd and even group counts and ragged last groups.
+    Filtered expectation: the oracle's full ranking post-filtered, as in
+    test_filtered_search."""
+    from matrixone_amd import engine
+    mmap = {"l2sq": orc.METRIC_L2SQ, "ip": orc.METRIC_IP,
+            "cos": orc.METRIC_COS, "l1": orc.METRIC_L1}
+    vecs, cents, assign, ids64, queries, allowed = _epilogue_data(d)
+    n, nlist, nq, probe, k = len(vecs), len(cents), len(queries), 4, 10
+    idx = orc.IvfIndex(cents, vecs, assign, ids=ids64)
+    byte = qtype in ("int8", "uint8")
+    vmin, vmax = np.percentile(vecs, 0.1), np.percentile(vecs, 99.9)
+
+    def oracle(kk):
+        if not byte:
+            return orc.ivf_search_half(idx, mmap[metric], queries, probe, kk,
+                                       bf16=(qtype == "bf16"))
+        uns = qtype == "uint8"
+        mul, add = (orc.uint8_params(vmin, vmax) if uns
+                    else orc.int8_params(vmin, vmax))
+        return orc.ivf_search_quantized(idx, mmap[metric], queries, probe, kk,
+                                        mul, add, unsigned=uns)
+
+    ix = engine.IvfFlatIndex(d, nlist, metric=metric, capacity=n, qtype=qtype)
+    ix.add(vecs, ids=ids64)
+    ix.set_centroids(cents)
+    ix.set_assignments(assign.astype(np.int32))
+    if byte:
+        ix.set_quantizer(vmin, vmax)
+    ix.build()
+    ctx = f"{qtype}/d{d}/{metric}/{'filtered' if filtered else 'all'}"
+    if not filtered:
+        ref_ids, ref_d = oracle(k)
+        ids, dists = ix.search(queries, k, probe)
+        _assert_parity(ids, dists, ref_ids, ref_d, ctx=ctx)
+    else:
+        all_ids, all_d = oracle(n)  # rank ALL candidates, keep allowed
+        aset = set(allowed.tolist())
+        exp_ids = np.full((nq, k), -1, dtype=np.int64)
+        exp_d = np.full((nq, k), np.finfo(np.float32).max, dtype=np.float32)
+        for i in range(nq):
+            keep = [(all_d[i, j], all_ids[i, j])
+                    for j in range(all_ids.shape[1])
+                    if all_ids[i, j] >= 0 and all_ids[i, j] in aset]
+            for j, (dd, ii) in enumerate(keep[:k]):
+                exp_ids[i, j] = ii
+                exp_d[i, j] = dd
+        gids, gdists = ix.search_filtered(queries, k, probe,
+                                          ix.filter_bitset(allowed))
+        np.testing.assert_array_equal(gids == -1, exp_ids == -1)
+        _assert_parity(gids, gdists, exp_ids, exp_d, ctx=ctx)
+    ix.close()
+
+
 def test_pred_filtered_search():
     """SQL residual-predicate gated search (§8f3): preds -> slot bitset
     (ADD-order columns permuted to slots) == the same search with an
