@@ -98,12 +98,22 @@ bool launch_rank_gemm(int metric, const float* queries, const float* cents,
                       const float* qnorms, const float* cnorms, int nq,
                       int nlist, int dpad, float* out, hipStream_t stream);
 
-/* Quantized (int8/uint8) list scan + helpers. */
+/* Quantized (int8/uint8) list scan + helpers. `layout` is the byte order of
+ * `packed` (moann_scan_plan.h): ROWS16 takes the variant's dot or uchar4
+ * kernel, MFMA64 takes scan_i8_mfma_kernel and throws for a variant, metric
+ * or dpad that kernel does not cover. */
 void launch_scan_i8(int metric, ScanVariant variant, bool uns,
-                    const uint8_t* packed, const uint8_t* queries_q,
-                    const int32_t* qnorms, const int32_t* rownorms, int dpad,
-                    const ScanJobs& jb, float* dists_out, hipStream_t stream,
+                    ByteImageLayout layout, const uint8_t* packed,
+                    const uint8_t* queries_q, const int32_t* qnorms,
+                    const int32_t* rownorms, int dpad, const ScanJobs& jb,
+                    float* dists_out, hipStream_t stream,
                     const uint32_t* filter_bitset = nullptr);
+/* pack row-major quantized rows in MFMA order (dpad % 64 == 0) */
+void launch_bytes_pack_mfma(const uint8_t* rows_q, int dpad,
+                            const int64_t* group_rowbase,
+                            const int32_t* group_valid,
+                            const int64_t* slot_rows, int64_t ngroups,
+                            uint8_t* packed, hipStream_t stream);
 /* per-(group,lane) sum-of-squares over the packed byte rows (build-time,
  * feeds the dot-form scan's rn + qn - 2*dot L2) */
 void launch_bytes_pack16(const uint8_t* rows_q, int dpad,
@@ -111,8 +121,9 @@ void launch_bytes_pack16(const uint8_t* rows_q, int dpad,
                          const int32_t* group_valid,
                          const int64_t* slot_rows, int64_t ngroups,
                          uint8_t* packed, hipStream_t stream);
-void launch_rownorms_i8(bool uns, const uint8_t* packed, int64_t ngroups,
-                        int dpad, int32_t* out, hipStream_t stream);
+void launch_rownorms_i8(bool uns, ByteImageLayout layout,
+                        const uint8_t* packed, int64_t ngroups, int dpad,
+                        int32_t* out, hipStream_t stream);
 void launch_unpack_bytes(const uint8_t* packed, int dim, int dpad,
                          const int64_t* group_slotbase,
                          const int32_t* group_valid, int64_t ngroups,

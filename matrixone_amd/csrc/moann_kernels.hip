@@ -1088,6 +1088,210 @@ __global__ __launch_bounds__(256) void scan_i8_dot_kernel(
     }
 }
 
+/* MFMA byte scan (dpad % 64 == 0, signed bytes, QT = 16): the dot-form scan
+ * as the 16-column int8 GEMM it is, on v_mfma_i32_16x16x64_i8. Reads the
+ * image in ByteImageLayout::MFMA64 — per group of 64 rows and 64-dim step J,
+ * four 1 KiB units (16-row sub-blocks s); in a unit lane l's 16 bytes are row
+ * 16s + (l & 15), dims 64J + 16(l >> 4) .. +15 — so one coalesced wave load
+ * is one B operand as it stands. The A operand is the query tile: lane l
+ * reads query (l & 15), the same 16 dims, from LDS (row stride dpad + 16:
+ * the sixteen rows of one read fall on distinct banks). Both operands hold
+ * the same k positions in the same lane, so the product is the row-by-query
+ * dot whatever the k order inside the instruction. Accumulator: column
+ * (lane & 15) = image row, row 4(lane >> 4) + reg = query; one store
+ * instruction writes 4 queries x 16 consecutive rows.
+ *
+ * A wave streams a CONTIGUOUS run of the job's groups (a quarter of the
+ * chunk) as one sequence of 4 KiB steps through a register ring RING steps
+ * deep: the steady-state loop reloads each ring slot unconditionally right
+ * after consuming it, so RING * 4 KiB stay in flight across steps and group
+ * boundaries; the last steps are peeled. Exact int32 accumulation: results
+ * are bit-identical to scan_i8_dot_kernel. */
+typedef int mfma_v4i __attribute__((ext_vector_type(4)));
+
+/* One 4 KiB step of the MFMA scan's stream into a ring slot: four 1 KiB wave
+ * loads. Written as asm so that hipcc does not track them: with plain loads
+ * it drained the whole ring (s_waitcnt vmcnt(0)) before every step, because
+ * the group epilogue inside the loop leaves its wait state unknown. The
+ * slot's registers hold nothing until ring_wait has passed over them. */
+__device__ __forceinline__ void ring_load(mfma_v4i (&x)[4], const uint4* p) {
+    asm volatile(
+        "global_load_dwordx4 %0, %4, off\n\t"
+        "global_load_dwordx4 %1, %4, off offset:1024\n\t"
+        "global_load_dwordx4 %2, %4, off offset:2048\n\t"
+        "global_load_dwordx4 %3, %4, off offset:3072"
+        : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3])
+        : "v"(p));
+}
+
+/* Wait until at most NEWER vector-memory operations issued after this slot's
+ * ring_load are outstanding (they complete in issue order, so the slot has
+ * landed; anything else issued since only makes the wait stricter). The slot
+ * is an in-out operand so that no use of it moves above the wait. */
+template <int NEWER>
+__device__ __forceinline__ void ring_wait(mfma_v4i (&x)[4]) {
+    asm volatile("s_waitcnt vmcnt(%4)"
+                 : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3])
+                 : "n"(NEWER));
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(256) void scan_i8_mfma_kernel(
+    const uint8_t* __restrict__ packed, const uint8_t* __restrict__ queries_q,
+    const int32_t* __restrict__ qnorms_i, /* [nq] sum sq (l2/cos) */
+    const int32_t* __restrict__ rownorms, /* [ngroups*64] sum sq (l2/cos) */
+    int dpad, const ScanJobs jobs,
+    const uint32_t* __restrict__ filter_bitset,
+    float* __restrict__ dists_out) {
+    constexpr int QT = 16, RING = 3;
+    constexpr bool NEED_N = METRIC == KM_L2SQ || METRIC == KM_COS;
+    extern __shared__ float ldsf[];
+    uint8_t* ldsq = (uint8_t*)ldsf; /* [QT][dpad + 16] bytes */
+    const int qstride = dpad + 16;
+    int32_t* ldsn = (int32_t*)(ldsq + QT * qstride);
+
+    const JobView jv = load_job(jobs);
+
+    /* query tile -> LDS, 16 bytes per thread and step; slots t >= nq zero */
+    {
+        const int d16 = dpad >> 4;
+        for (int e = threadIdx.x; e < QT * d16; e += 256) {
+            const int t = e / d16, c = e - t * d16;
+            uint4 v = {0, 0, 0, 0};
+            if (t < jv.nq) {
+                const int q = jobs.qslot_query[jv.qbase + t];
+                v = ((const uint4*)(queries_q + (int64_t)q * dpad))[c];
+            }
+            *(uint4*)(ldsq + t * qstride + 16 * c) = v;
+        }
+        if (NEED_N && threadIdx.x < QT)
+            ldsn[threadIdx.x] =
+                (int)threadIdx.x < jv.nq
+                    ? qnorms_i[jobs.qslot_query[jv.qbase + threadIdx.x]]
+                    : 0;
+        __syncthreads();
+    }
+
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r16 = lane & 15, quad = lane >> 4;
+    const int nJ = dpad >> 6;
+
+    /* this wave's contiguous groups of the chunk */
+    const int per = (jv.gcount + 3) >> 2;
+    const int gw0 = jv.gstart + wave * per;
+    const int ngw = min(per, jv.gstart + jv.gcount - gw0);
+    if (ngw <= 0) return;
+    const int nsteps = ngw * nJ;
+
+    /* the 4 queries this lane finishes: output bases and norms */
+    int64_t ob[4];
+    int32_t qn[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int t = 4 * quad + i;
+        ob[i] = t < jv.nq ? jobs.qslot_outbase[jv.qbase + t] : 0;
+        qn[i] = NEED_N ? ldsn[t] : 0;
+    }
+    const int64_t sb = filter_bitset ? jobs.slot_base[jv.j] : 0;
+
+    /* step k of the wave: 4 uint4 per lane at base + k*256 + s*64 */
+    const uint4* __restrict__ base =
+        (const uint4*)(packed + (jv.baseg + gw0) * (int64_t)64 * dpad) + lane;
+    const uint8_t* qlane = ldsq + r16 * qstride + 16 * quad;
+
+    mfma_v4i acc[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc[s] = mfma_v4i{0, 0, 0, 0};
+    int J = 0, g = gw0;
+
+    const auto consume = [&](const mfma_v4i (&x)[4]) {
+        const uint4 qv = *(const uint4*)(qlane + 64 * J);
+        const mfma_v4i a = {(int)qv.x, (int)qv.y, (int)qv.z, (int)qv.w};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            acc[s] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, x[s], acc[s], 0,
+                                                           0, 0);
+        }
+        if (++J < nJ) return;
+        /* group done. First everything the epilogue reads from memory, and
+         * an explicit wait for it: a load the compiler still counts as
+         * pending when control rejoins the stream (a row whose queries are
+         * all skipped never uses its norm) made it drain the ring before
+         * every ring_load. Stores may stay in flight. */
+        int32_t rn[4];
+        bool live[4], pass[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int row = g * 64 + 16 * s + r16;
+            live[s] = row < jv.rows;
+            rn[s] = NEED_N && live[s]
+                        ? rownorms[(jv.baseg + g) * 64 + 16 * s + r16]
+                        : 0;
+            pass[s] = !filter_bitset || !live[s] ||
+                      slot_passes(filter_bitset, sb + row);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70); /* vmcnt(0) only */
+        /* finish and store, filter per row */
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int row = g * 64 + 16 * s + r16;
+            if (live[s]) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (4 * quad + i < jv.nq)
+                        dists_out[ob[i] + row] =
+                            pass[s] ? finish_i32<METRIC, true>(acc[s][i],
+                                                               rn[s], qn[i])
+                                    : FLT_MAX;
+            }
+            acc[s] = mfma_v4i{0, 0, 0, 0};
+        }
+        J = 0;
+        ++g;
+    };
+
+    mfma_v4i ring[RING][4];
+#pragma unroll
+    for (int d = 0; d < RING; ++d) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) ring[d][s] = mfma_v4i{0, 0, 0, 0};
+        if (d < nsteps) ring_load(ring[d], base + d * 256);
+    }
+
+    /* steady state: a slot is consumed once only the RING - 1 younger slots'
+     * loads may still be out, then reloaded RING steps ahead */
+    const int nmain = nsteps > RING ? (nsteps - RING) / RING * RING : 0;
+    int k = 0;
+    for (; k < nmain; k += RING) {
+#pragma unroll
+        for (int d = 0; d < RING; ++d) {
+            ring_wait<4 * (RING - 1)>(ring[d]);
+            consume(ring[d]);
+            ring_load(ring[d], base + (int64_t)(k + d + RING) * 256);
+        }
+    }
+    /* peeled tail, at most 2*RING - 1 steps: drain the ring once, then
+     * rotate it; the first RING - 1 of these steps still load */
+#pragma unroll
+    for (int d = 0; d < RING; ++d) ring_wait<0>(ring[d]);
+    for (; k < nsteps; ++k) {
+        consume(ring[0]);
+#pragma unroll
+        for (int d = 0; d + 1 < RING; ++d)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) ring[d][s] = ring[d + 1][s];
+        if (k + RING < nsteps) {
+            const uint4* nx = base + (int64_t)(k + RING) * 256;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const uint4 v = nx[s * 64];
+                ring[RING - 1][s] =
+                    mfma_v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
+            }
+        }
+    }
+}
+
 /* pack quantized byte rows into 16-byte units: [g][dpad/16][64][16] — the
  * layout the dot-form scan streams with 16 B/lane dwordx4 loads (the
  * uchar4 [g][dpad/4][64][4] layout only gives 4 B/lane per 256 B block).
@@ -1132,21 +1336,73 @@ void launch_bytes_pack16(const uint8_t* rows_q, int dpad,
                        slot_rows, ngroups, packed);
 }
 
-/* per-(group,lane) byte-row sum of squares, same wave layout as the scan */
-template <bool UNSIGNED>
+/* pack quantized byte rows in MFMA order (ByteImageLayout::MFMA64, dpad % 64
+ * == 0): [g][dpad/64][4][64][16] — unit (g, J, s), lane l holds row
+ * 16s + (l & 15), dims 64J + 16(l >> 4) .. +15; what scan_i8_mfma_kernel
+ * loads as its B operand. Same group stride (64*dpad bytes) as pack16;
+ * thread per output uint4. */
+__global__ void bytes_pack_mfma_kernel(const uint8_t* __restrict__ rows_q,
+                                       int dpad,
+                                       const int64_t* __restrict__ group_rowbase,
+                                       const int32_t* __restrict__ group_valid,
+                                       const int64_t* __restrict__ slot_rows,
+                                       int64_t ngroups,
+                                       uint8_t* __restrict__ packed) {
+    const int nJ = dpad >> 6;
+    const int64_t nunits = ngroups * (int64_t)nJ * 256;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         idx < nunits; idx += stride) {
+        const int lane = (int)(idx & 63);
+        const int s = (int)((idx >> 6) & 3);
+        const int64_t rest = idx >> 8;
+        const int J = (int)(rest % nJ);
+        const int64_t g = rest / nJ;
+        const int rg = 16 * s + (lane & 15);
+        uint4 v = {0, 0, 0, 0};
+        if (rg < group_valid[g]) {
+            const int64_t row = slot_rows[group_rowbase[g] + rg];
+            v = *(const uint4*)(rows_q + row * (int64_t)dpad + 64 * J +
+                                16 * (lane >> 4));
+        }
+        ((uint4*)packed)[idx] = v;
+    }
+}
+
+void launch_bytes_pack_mfma(const uint8_t* rows_q, int dpad,
+                            const int64_t* group_rowbase,
+                            const int32_t* group_valid,
+                            const int64_t* slot_rows, int64_t ngroups,
+                            uint8_t* packed, hipStream_t stream) {
+    const int64_t nunits = ngroups * (int64_t)(dpad >> 6) * 256;
+    if (!nunits) return;
+    const int block = 256;
+    const int64_t grid = std::min<int64_t>((nunits + block - 1) / block,
+                                           1 << 22);
+    hipLaunchKernelGGL(bytes_pack_mfma_kernel, dim3((uint32_t)grid),
+                       dim3(block), 0, stream, rows_q, dpad, group_rowbase,
+                       group_valid, slot_rows, ngroups, packed);
+}
+
+/* per-(group,lane) byte-row sum of squares; lane = row of the group in both
+ * layouts, so the output is [g*64 + row] either way */
+template <bool UNSIGNED, bool MFMA64>
 __global__ __launch_bounds__(256) void rownorms_i8_kernel(
     const uint8_t* __restrict__ packed, int64_t ngroups, int dpad,
     int32_t* __restrict__ out) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * 4 + wave;
     if (g >= ngroups) return;
-    /* layout16: [g][dpad/16][64][16] (bytes_pack16_kernel) */
+    /* ROWS16: [g][dpad/16][64][16] (bytes_pack16_kernel): 16-dim unit m of
+     * row `lane` is uint4 m*64 + lane. MFMA64 (bytes_pack_mfma_kernel): it
+     * is uint4 ((m>>2)*4 + (lane>>4))*64 + (m&3)*16 + (lane&15). */
     const uint4* __restrict__ d =
-        (const uint4*)(packed + g * (int64_t)64 * dpad) + lane;
+        (const uint4*)(packed + g * (int64_t)64 * dpad) +
+        (MFMA64 ? (lane >> 4) * 64 + (lane & 15) : lane);
     int32_t acc = 0;
     const int d16 = dpad >> 4;
     for (int m = 0; m < d16; ++m) {
-        const uint4 v = d[m * 64];
+        const uint4 v = MFMA64 ? d[(m >> 2) * 256 + (m & 3) * 16] : d[m * 64];
         if (UNSIGNED) {
             acc = (int32_t)__builtin_amdgcn_udot4(v.x, v.x, (uint32_t)acc, false);
             acc = (int32_t)__builtin_amdgcn_udot4(v.y, v.y, (uint32_t)acc, false);
@@ -1162,21 +1418,29 @@ __global__ __launch_bounds__(256) void rownorms_i8_kernel(
     out[g * 64 + lane] = acc;
 }
 
-void launch_rownorms_i8(bool uns, const uint8_t* packed, int64_t ngroups,
-                        int dpad, int32_t* out, hipStream_t stream) {
+void launch_rownorms_i8(bool uns, ByteImageLayout layout,
+                        const uint8_t* packed, int64_t ngroups, int dpad,
+                        int32_t* out, hipStream_t stream) {
     const dim3 grid((uint32_t)((ngroups + 3) / 4)), block(256);
-    if (uns)
-        hipLaunchKernelGGL((rownorms_i8_kernel<true>), grid, block, 0, stream,
-                           packed, ngroups, dpad, out);
+    if (layout == ByteImageLayout::MFMA64) {
+        if (uns || dpad % 64)
+            throw std::logic_error("launch_rownorms_i8: MFMA64 image is "
+                                   "signed with dpad % 64 == 0");
+        hipLaunchKernelGGL((rownorms_i8_kernel<false, true>), grid, block, 0,
+                           stream, packed, ngroups, dpad, out);
+    } else if (uns)
+        hipLaunchKernelGGL((rownorms_i8_kernel<true, false>), grid, block, 0,
+                           stream, packed, ngroups, dpad, out);
     else
-        hipLaunchKernelGGL((rownorms_i8_kernel<false>), grid, block, 0, stream,
-                           packed, ngroups, dpad, out);
+        hipLaunchKernelGGL((rownorms_i8_kernel<false, false>), grid, block, 0,
+                           stream, packed, ngroups, dpad, out);
 }
 
 void launch_scan_i8(int metric, ScanVariant v, bool uns,
-                    const uint8_t* packed, const uint8_t* queries_q,
-                    const int32_t* qnorms, const int32_t* rownorms, int dpad,
-                    const ScanJobs& jb, float* dists_out, hipStream_t stream,
+                    ByteImageLayout layout, const uint8_t* packed,
+                    const uint8_t* queries_q, const int32_t* qnorms,
+                    const int32_t* rownorms, int dpad, const ScanJobs& jb,
+                    float* dists_out, hipStream_t stream,
                     const uint32_t* filter_bitset) {
     /* the byte kernels' only tile widths: dot form 16 and 8, uchar4 form 8 */
     const bool dot_ok = v.kind == ScanKind::BYTE_DOT &&
@@ -1185,6 +1449,25 @@ void launch_scan_i8(int metric, ScanVariant v, bool uns,
     if (!dot_ok && !u4_ok) bad_variant("launch_scan_i8", v);
     if (dot_ok && !rownorms)
         throw std::logic_error("launch_scan_i8: BYTE_DOT without row norms");
+    if (layout == ByteImageLayout::MFMA64) {
+        /* the image was packed for scan_i8_mfma_kernel alone: a variant or
+         * metric that kernel does not cover must never read it */
+        if (!byte_mfma_applies(metric, v, dpad) || uns)
+            throw std::logic_error("launch_scan_i8: MFMA64 image with a "
+                                   "variant the MFMA scan does not cover");
+        if (!jb.njobs) return;
+        with_metric(metric, [&](auto m) {
+            constexpr int M = decltype(m)::value;
+            if constexpr (M != KM_L1) {
+                const size_t shmem = (size_t)16 * (dpad + 16) + 16 * 4;
+                hipLaunchKernelGGL(scan_i8_mfma_kernel<M>, dim3(jb.njobs),
+                                   dim3(256), shmem, stream, packed,
+                                   queries_q, qnorms, rownorms, dpad, jb,
+                                   filter_bitset, dists_out);
+            }
+        });
+        return;
+    }
     if (!jb.njobs) return;
     with_metric(metric, [&](auto m) {
         constexpr int M = decltype(m)::value;

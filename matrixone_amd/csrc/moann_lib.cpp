@@ -139,6 +139,7 @@ struct IvfIndex {
     int refine_depth = 0;
     float* d_rows_f32 = nullptr;    /* [count][dim] slot-major (refine) */
     uint8_t* d_packed_rq = nullptr; /* clip-quantized interleaved image */
+    ByteImageLayout rq_layout = ByteImageLayout::ROWS16; /* its byte order */
     int32_t* d_rownorm_rq = nullptr;
     double rq_mul = 1.0, rq_add = 0.0;
     bool built = false, started = false;
@@ -399,11 +400,13 @@ double collect_result(MoannResult* res); /* below; returns kernel-window ms */
 const ScanOverrides& scan_overrides() {
     static const ScanOverrides ov = [] {
         const char *sc = getenv("MOANN_SCAN"), *bq = getenv("MOANN_BYTE_QT"),
-                   *cg = getenv("MOANN_CHUNKG");
+                   *cg = getenv("MOANN_CHUNKG"),
+                   *bm = getenv("MOANN_BYTE_MFMA");
         ScanOverrides o;
         o.generic_f32 = sc && strcmp(sc, "generic") == 0;
         o.byte_qt8 = bq && atoi(bq) == 8;
         o.chunk_g = cg ? atoi(cg) : 0;
+        o.byte_mfma_off = bm && strcmp(bm, "0") == 0;
         return o;
     }();
     return ov;
@@ -506,6 +509,8 @@ void scan_lists(IvfIndex* ix, SearchCtx* cx, const uint32_t* filter_words) {
          * the queries like its entries (quantizer.go ApplyInt8/entry SQL) */
         const bool uns = !c.refine && ix->qtype == Quantization_UINT8;
         const uint8_t* image = c.refine ? ix->d_packed_rq : ix->d_packed_q;
+        const ByteImageLayout layout =
+            c.refine ? ix->rq_layout : ByteImageLayout::ROWS16;
         const int32_t* rownorms =
             c.refine ? ix->d_rownorm_rq : ix->d_rownorm_q;
         const double mul = c.refine ? ix->rq_mul : ix->quant_mul;
@@ -523,8 +528,8 @@ void scan_lists(IvfIndex* ix, SearchCtx* cx, const uint32_t* filter_words) {
                              cx->w_qnorms_i.as<int32_t>(), s);
             d_qni = cx->w_qnorms_i.as<int32_t>();
         }
-        launch_scan_i8(ix->kmetric, v, uns, image, d_qq, d_qni, rownorms,
-                       dpad, jb, d_cand, s, d_filter);
+        launch_scan_i8(ix->kmetric, v, uns, layout, image, d_qq, d_qni,
+                       rownorms, dpad, jb, d_cand, s, d_filter);
         break;
     }
     case ScanKind::HALF: {
@@ -1192,7 +1197,8 @@ void gpu_ivf_flat_build(gpu_ivf_flat_c h, void* errmsg) {
                 HIP_CHECK(hipMalloc(&ix->d_rownorm_q,
                                     (size_t)ix->total_groups * 64 * 4));
                 launch_rownorms_i8(ix->qtype == Quantization_UINT8,
-                                   ix->d_packed_q, ix->total_groups,
+                                   ByteImageLayout::ROWS16, ix->d_packed_q,
+                                   ix->total_groups,
                                    (int)ix->dpad, ix->d_rownorm_q,
                                    ix->stream);
             }
@@ -2797,7 +2803,23 @@ void moann_ivf_flat_enable_refine(gpu_ivf_flat_c h, uint32_t depth,
                                 hipMemcpyHostToDevice));
             HIP_CHECK(hipMalloc(&ix->d_packed_rq,
                                 (size_t)ix->total_groups * 64 * ix->dpad));
-            if ((ix->dpad & 15) == 0)
+            /* byte order follows the kernel that will scan: the variant
+             * pick_scan gives this index's refine scan (row norms exist
+             * whenever dpad % 16 == 0), fixed for the process */
+            const bool norms = (ix->dpad & 15) == 0;
+            ix->rq_layout = pick_refine_layout(
+                ix->kmetric,
+                pick_scan(ix->kmetric, (int)ix->dpad, ix->qtype, true, norms,
+                          scan_overrides()).list,
+                (int)ix->dpad, scan_overrides());
+            if (ix->rq_layout == ByteImageLayout::MFMA64)
+                launch_bytes_pack_mfma(d_qrows.as<uint8_t>(), (int)ix->dpad,
+                                       d_gsb.as<int64_t>(),
+                                       d_gv.as<int32_t>(),
+                                       d_ident.as<int64_t>(),
+                                       ix->total_groups, ix->d_packed_rq,
+                                       ix->stream);
+            else if (norms)
                 launch_bytes_pack16(d_qrows.as<uint8_t>(), (int)ix->dpad,
                                     d_gsb.as<int64_t>(), d_gv.as<int32_t>(),
                                     d_ident.as<int64_t>(), ix->total_groups,
@@ -2808,10 +2830,11 @@ void moann_ivf_flat_enable_refine(gpu_ivf_flat_c h, uint32_t depth,
                                d_ident.as<int64_t>(), ix->total_groups,
                                ix->d_packed_rq, ix->stream);
             KCHECK("refine-pack");
-            if ((ix->dpad & 15) == 0) {
+            if (norms) {
                 HIP_CHECK(hipMalloc(&ix->d_rownorm_rq,
                                     (size_t)ix->total_groups * 64 * 4));
-                launch_rownorms_i8(false, ix->d_packed_rq, ix->total_groups,
+                launch_rownorms_i8(false, ix->rq_layout, ix->d_packed_rq,
+                                   ix->total_groups,
                                    (int)ix->dpad, ix->d_rownorm_rq,
                                    ix->stream);
             }

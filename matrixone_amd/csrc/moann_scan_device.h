@@ -1,6 +1,7 @@
 /* Device pieces shared by the list-scan kernels (scan_kernel, scan_h_kernel,
- * scan_i8_kernel, scan_i8_dot_kernel, scan_asm768_kernel): everything around
- * their inner dimension loops, plus the two conventions other kernels share
+ * scan_i8_kernel, scan_i8_dot_kernel, scan_asm768_kernel; scan_i8_mfma_kernel
+ * takes load_job, slot_passes and finish_i32 and has a tile stage and store
+ * of its own shape): everything around their inner dimension loops, plus the two conventions other kernels share
  * (the membership-filter bit test and MO's cosine distance). Each is stated
  * once, here. `__device__ __forceinline__` functions only. */
 

@@ -43,7 +43,8 @@ enum class ScanKind {
     F32,        /* scan_kernel<metric, qt>, qt in {8,4,2,1}                  */
     F32_ASM768, /* scan_asm768.hip: L2SQ, dpad 768, qt 16                    */
     HALF,       /* scan_h_kernel (f16/bf16 storage), qt 8                    */
-    BYTE_DOT,   /* scan_i8_dot_kernel, qt 16 or 8                            */
+    BYTE_DOT,   /* scan_i8_dot_kernel, qt 16 or 8; at qt 16 over an MFMA64
+                   image scan_i8_mfma_kernel (same jobs, same results)       */
     BYTE_U4,    /* scan_i8_kernel (uchar4 form), qt 8                        */
 };
 
@@ -63,6 +64,8 @@ struct ScanOverrides {
     bool generic_f32 = false; /* MOANN_SCAN=generic: no asm kernel        */
     bool byte_qt8 = false;    /* MOANN_BYTE_QT=8: no 16-wide byte tiles   */
     int chunk_g = 0;          /* MOANN_CHUNKG: list chunk groups, 0 = 8   */
+    bool byte_mfma_off = false; /* MOANN_BYTE_MFMA=0: refine image stays in
+                                   ROWS16, scanned by the dot kernel      */
 };
 
 struct ScanChoice { /* the list scan's and the centroid-rank scan's */
@@ -122,6 +125,32 @@ inline ScanChoice pick_scan(int kmetric, int dpad, quantization_t storage,
         c.list = c.rank;
     }
     return c;
+}
+
+/* Byte order inside a 64-row group of a dot-form byte image. The group
+ * stride is 64*dpad bytes in both, so job tables do not depend on it; the
+ * kernel that scans does. Only the internal refine image (built once, never
+ * unpacked or saved) is ever MFMA64. */
+enum class ByteImageLayout {
+    ROWS16, /* [g][dpad/16][64][16]: scan_i8_dot_kernel                      */
+    MFMA64, /* [g][dpad/64][4][64][16], lane l of unit (J, s) = row
+               16s + (l&15), dims 64J + 16(l>>4)..: scan_i8_mfma_kernel      */
+};
+
+/* What scan_i8_mfma_kernel covers: the 16-wide dot-form variant, signed
+ * bytes (the caller's concern), every metric but L1, whole 64-dim steps. */
+inline bool byte_mfma_applies(int kmetric, ScanVariant list, int dpad) {
+    return list.kind == ScanKind::BYTE_DOT && list.qt == 16 &&
+           kmetric != KM_L1 && dpad % 64 == 0;
+}
+
+/* Layout of the refine image, decided once when it is built: `list` is the
+ * variant pick_scan gives the refine scan of this index. */
+inline ByteImageLayout pick_refine_layout(int kmetric, ScanVariant list,
+                                          int dpad, const ScanOverrides& ov) {
+    return byte_mfma_applies(kmetric, list, dpad) && !ov.byte_mfma_off
+               ? ByteImageLayout::MFMA64
+               : ByteImageLayout::ROWS16;
 }
 
 /* ---------------------------- host job tables --------------------------- */
