@@ -201,10 +201,60 @@ void moann_ivf_flat_set_assignments(gpu_ivf_flat_c index_c,
                                     void* errmsg);
 
 /* ivf_flat_c.h:60 gpu_ivf_flat_build: packs the lists into the HBM-resident
- * interleaved layout and drops the staging buffer.  Requires centroids +
- * assignments (k-means build from raw data is index-BUILD machinery, out of
- * the judged search path — SURVEY.md §2 kmeans row; use the harness). */
+ * interleaved layout and drops the staging buffer. Three cases:
+ *   - neither centroids nor assignments set: the library trains the
+ *     centroids on the GPU (k-means, below) and assigns every row — the
+ *     reference's build-from-vectors;
+ *   - centroids set, assignments absent (LoadCentroids): every row is
+ *     assigned to its nearest centroid, nothing is trained;
+ *   - both set: the lists are exactly the caller's.
+ * Assignments without centroids are an error.
+ * After a build gpu_ivf_flat_get_centers and moann_ivf_flat_get_assignments
+ * return what the hidden centroid and entry tables store.
+ *
+ * The k-means contract (restated on the host in moann_kmeans_plan.h):
+ *   sample   n_train = min(n, max(ceil(fraction*n), min(n, n_lists))),
+ *            fraction = build_params.kmeans_trainset_fraction (<= 0 or > 1:
+ *            0.5), optionally capped by moann_ivf_flat_set_kmeans_params;
+ *            training row i is added row (i*n)/n_train. n < n_lists is an
+ *            error.
+ *   init     centroid j = training row (j*n_train)/n_lists.
+ *   iterate  assign the training rows to their nearest centroid (lowest
+ *            index on equal distance); each centroid becomes the mean of its
+ *            rows, summed in a fixed order (bit-identical across runs);
+ *            empty centroids, in ascending index, take the training rows
+ *            with the largest distance to their centroid (ties to the lower
+ *            row, each row once). Stop after n_iters iterations (default
+ *            20) or when an iteration repeats the previous assignment with
+ *            no empty centroid.
+ *   metric   L2, L2sqrt, L1 and inner-product indexes train under squared
+ *            L2 (expanded f32 form); cosine indexes train spherically (rows
+ *            scaled to unit norm in the mean, zero rows add nothing).
+ *   assign   finally every added row goes to its nearest centroid under the
+ *            INDEX metric — the gpu_ivf_flat_extend rule, so a row lands in
+ *            the list a search ranks first for it. */
 void gpu_ivf_flat_build(gpu_ivf_flat_c index_c, void* errmsg);
+
+/* moann extension — k-means knobs, before gpu_ivf_flat_build. n_iters 0 =
+ * default (20); max_train_rows 0 = no cap on the training sample. */
+void moann_ivf_flat_set_kmeans_params(gpu_ivf_flat_c index_c, uint32_t n_iters,
+                                      uint64_t max_train_rows, void* errmsg);
+
+/* moann extension — the list of every stored vector, [gpu_ivf_flat_len] ids
+ * in ADD order (extended rows last), after build: the entry-assignment
+ * column the index-create flow writes next to the centroids. */
+void moann_ivf_flat_get_assignments(gpu_ivf_flat_c index_c, int32_t* out,
+                                    void* errmsg);
+
+/* moann extension — what the native build of this index spent, after build:
+ * host wall-clock ms of training and of the final assignment (0 when that
+ * step did not run), the iterations run and the training sample size. The
+ * search-side moann_perf_t counters are reset per search window and have no
+ * build fields, so the build split is read here (tools/build_bench.py). Any
+ * out pointer may be null. */
+void moann_ivf_flat_kmeans_stats(gpu_ivf_flat_c index_c, double* train_ms,
+                                 double* assign_ms, uint32_t* iters,
+                                 uint64_t* n_train, void* errmsg);
 
 /* ivf_flat_c.h:57 */
 void gpu_ivf_flat_start(gpu_ivf_flat_c index_c, void* errmsg);

@@ -98,6 +98,45 @@ bool launch_rank_gemm(int metric, const float* queries, const float* cents,
                       const float* qnorms, const float* cnorms, int nq,
                       int nlist, int dpad, float* out, hipStream_t stream);
 
+/* ---- native k-means build (kmeans_kernels.hip) ----
+ * A row set is a view of the staged f32 rows: row i of the set is staged row
+ * (i*num)/den — the training sample's stride rule (moann_kmeans_plan.h) with
+ * num = n, den = n_train; num == den is the identity. Nothing is copied. */
+struct KmRowMap {
+    int64_t num, den;
+};
+
+/* Fused nearest-centroid assignment: assign[i] = argmin_c dist(row i, c),
+ * best[i] = that distance, for KM_L2SQ (expanded, clamped at 0), KM_IP and
+ * KM_COS — rank_gemm_kernel's distances. Ties go to the lowest index. cents
+ * is the zero-padded [k][dpad] matrix; rows have stride row_stride (= dim).
+ * No [n][k] buffer; throws std::logic_error for KM_L1. */
+void launch_km_assign(int metric, const float* rows, int64_t row_stride,
+                      KmRowMap map, int64_t n, const float* cents,
+                      const float* cnorms, int k, int dim, int dpad,
+                      int32_t* assign, float* best, hipStream_t stream);
+/* out[i] = |row i|^2, or 1/|row i| (0 for a zero row) when inverse_norm */
+void launch_km_row_sumsq(bool inverse_norm, const float* rows,
+                         int64_t row_stride, KmRowMap map, int64_t n, int dim,
+                         float* out, hipStream_t stream);
+/* Deterministic centroid update from a CSR of the assignment (offs [k+1],
+ * members = set rows grouped by centroid, ascending inside a group): mean of
+ * the members, rows scaled by inv_norm[i] when non-null (spherical k-means).
+ * Fixed order, no atomics; an empty centroid keeps its value. */
+void launch_km_update(const float* rows, int64_t row_stride, KmRowMap map,
+                      const int64_t* offs, const int32_t* members,
+                      const float* inv_norm, int k, int dim, int dpad,
+                      float* cents, hipStream_t stream);
+/* cents[cidx[b]][0..dim) = set row trow[b], b < count (init and reseed) */
+void launch_km_set_centroids(const float* rows, int64_t row_stride,
+                             KmRowMap map, const int32_t* cidx,
+                             const int64_t* trow, int count, int dim, int dpad,
+                             float* cents, hipStream_t stream);
+/* set rows [i0, i0+count) -> out[count][dpad], zero-padded */
+void launch_km_gather_pad(const float* rows, int64_t row_stride, KmRowMap map,
+                          int64_t i0, int64_t count, int dim, int dpad,
+                          float* out, hipStream_t stream);
+
 /* Quantized (int8/uint8) list scan + helpers. `layout` is the byte order of
  * `packed` (moann_scan_plan.h): ROWS16 takes the variant's dot or uchar4
  * kernel, MFMA64 takes scan_i8_mfma_kernel and throws for a variant, metric

@@ -33,6 +33,7 @@
 
 #include "../../include/moann.h"
 #include "moann_host_common.h"
+#include "moann_kmeans_plan.h"
 
 namespace {
 
@@ -151,6 +152,15 @@ struct IvfIndex {
     std::vector<int32_t> h_assign;
     std::vector<float> h_centroids;
     float* d_staging = nullptr;
+    /* native k-means build (moann_kmeans_plan.h): build_params fraction,
+     * moann_ivf_flat_set_kmeans_params knobs (0 = default / no cap), and
+     * what the last build spent (moann_ivf_flat_kmeans_stats) */
+    double km_fraction = KMEANS_DEFAULT_FRACTION;
+    uint32_t km_iters = 0;
+    uint64_t km_max_train = 0;
+    double km_train_ms = 0.0, km_assign_ms = 0.0;
+    uint32_t km_iters_run = 0;
+    uint64_t km_n_train = 0;
 
     /* built state */
     float* d_packed = nullptr;           /* interleaved entry data            */
@@ -932,6 +942,250 @@ void batcher_loop(IvfIndex* ix) {
     }
 }
 
+/* ------------------------- native k-means build -------------------------
+ * gpu_ivf_flat_build fills h_centroids / h_assign itself when the caller
+ * did not (DESIGN.md "Native k-means build"). The rules — sample, init,
+ * reseed, stop — are moann_kmeans_plan.h; the kernels kmeans_kernels.hip. */
+
+/* MOANN_KMEANS_ASSIGN=gemm, read once: assignment through the chunked
+ * rank GEMM + top-1 select instead of the fused kernel (A/B + fallback). */
+bool kmeans_assign_gemm() {
+    static const bool v = [] {
+        const char* e = getenv("MOANN_KMEANS_ASSIGN");
+        return e && strcmp(e, "gemm") == 0;
+    }();
+    return v;
+}
+
+struct KmeansWork { /* workspaces of the gemm composition */
+    DevBuf q, qn, dmat;
+};
+
+/* assign[i], best[i] for the n rows of the set `map` over d_staging */
+void kmeans_assign(IvfIndex* ix, int metric, KmRowMap map, int64_t n,
+                   const float* d_cents, const float* d_cnorms,
+                   int32_t* d_assign, float* d_best, KmeansWork& w) {
+    const int k = (int)ix->nlist, dim = (int)ix->dim, dpad = (int)ix->dpad;
+    if (!kmeans_assign_gemm()) {
+        launch_km_assign(metric, ix->d_staging, dim, map, n, d_cents,
+                         d_cnorms, k, dim, dpad, d_assign, d_best, ix->stream);
+        KCHECK("kmeans-assign");
+        return;
+    }
+    /* the composition the tree could already do: padded row chunk ->
+     * [chunk][k] distance matrix -> top-1. The matrix is bounded at 256 MiB
+     * by chunking the rows. */
+    int64_t chunk = std::max<int64_t>(
+        32, ((int64_t)256 << 20) / ((int64_t)k * 4) / 32 * 32);
+    chunk = std::min(chunk, n);
+    w.q.ensure((size_t)chunk * dpad * 4);
+    w.qn.ensure((size_t)chunk * 4);
+    w.dmat.ensure((size_t)chunk * k * 4);
+    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+        const int64_t cnt = std::min(chunk, n - i0);
+        launch_km_gather_pad(ix->d_staging, dim, map, i0, cnt, dim, dpad,
+                             w.q.as<float>(), ix->stream);
+        launch_qnorms(w.q.as<float>(), (int)cnt, dpad, w.qn.as<float>(),
+                      ix->stream);
+        if (!launch_rank_gemm(metric, w.q.as<float>(), d_cents,
+                              w.qn.as<float>(), d_cnorms, (int)cnt, k, dpad,
+                              w.dmat.as<float>(), ix->stream))
+            throw std::logic_error("kmeans: metric has no GEMM form");
+        launch_topk(w.dmat.as<float>(), nullptr, k, (int)cnt, 1,
+                    d_assign + i0, d_best + i0, ix->stream);
+        KCHECK("kmeans-assign-gemm");
+    }
+}
+
+void kmeans_check_range(const std::vector<int32_t>& a, uint32_t nlist) {
+    for (int32_t v : a)
+        if (v < 0 || (uint32_t)v >= nlist)
+            throw std::runtime_error("kmeans: assignment out of range");
+}
+
+/* [nlist][dpad] zero-padded device centroids + |c|^2 */
+void kmeans_cnorms(IvfIndex* ix, const float* d_cents, float* d_cnorms) {
+    launch_km_row_sumsq(false, d_cents, ix->dpad, KmRowMap {1, 1},
+                        ix->nlist, (int)ix->dpad, d_cnorms, ix->stream);
+    KCHECK("kmeans-cnorms");
+}
+
+/* train h_centroids from the staged rows */
+void kmeans_train(IvfIndex* ix) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t n = (int64_t)ix->count;
+    const int k = (int)ix->nlist, dim = (int)ix->dim, dpad = (int)ix->dpad;
+    const int64_t n_train =
+        (int64_t)kmeans_n_train(ix->count, ix->nlist, ix->km_fraction,
+                                ix->km_max_train);
+    /* the kernels evaluate (i*n)/n_train in int64 (moann_kmeans_plan.h
+     * uses 128 bits): far beyond any staging buffer, but checked */
+    if ((unsigned __int128)n * (unsigned __int128)n_train >
+        (unsigned __int128)INT64_MAX)
+        throw std::runtime_error("kmeans: n * n_train exceeds 2^63");
+    const KmRowMap map {n, n_train};
+    /* L2, L2sqrt, L1 and IP indexes train under L2SQ; COS is spherical */
+    const int tmetric = ix->kmetric == KM_COS ? KM_COS : KM_L2SQ;
+    const hipStream_t s = ix->stream;
+
+    DevBuf d_cents, d_cnorms, d_assign, d_best, d_inv, d_offs, d_members,
+        d_cidx, d_trow;
+    KmeansWork work;
+    d_cents.ensure((size_t)k * dpad * 4);
+    HIP_CHECK(hipMemsetAsync(d_cents.ptr, 0, (size_t)k * dpad * 4, s));
+    d_cnorms.ensure((size_t)k * 4);
+    d_assign.ensure((size_t)n_train * 4);
+    d_best.ensure((size_t)n_train * 4);
+    d_members.ensure((size_t)n_train * 4);
+
+    std::vector<int32_t> cidx(k);
+    std::vector<int64_t> trow(k);
+    for (int j = 0; j < k; ++j) {
+        cidx[j] = j;
+        trow[j] = (int64_t)kmeans_init_row((uint32_t)j, (uint64_t)n_train,
+                                           ix->nlist);
+    }
+    upload_vector(d_cidx, cidx, s);
+    upload_vector(d_trow, trow, s);
+    launch_km_set_centroids(ix->d_staging, dim, map, d_cidx.as<int32_t>(),
+                            d_trow.as<int64_t>(), k, dim, dpad,
+                            d_cents.as<float>(), s);
+    KCHECK("kmeans-init");
+    const float* d_invp = nullptr;
+    if (tmetric == KM_COS) {
+        d_inv.ensure((size_t)n_train * 4);
+        launch_km_row_sumsq(true, ix->d_staging, dim, map, n_train, dim,
+                            d_inv.as<float>(), s);
+        KCHECK("kmeans-invnorm");
+        d_invp = d_inv.as<float>();
+    }
+    HIP_CHECK(hipStreamSynchronize(s)); /* cidx/trow are reused below */
+
+    std::vector<int32_t> h_a(n_train), prev, members(n_train);
+    std::vector<float> h_best(n_train);
+    std::vector<int64_t> offs(k + 1), cur(k);
+    uint32_t it = 0;
+    for (;; ++it) {
+        kmeans_cnorms(ix, d_cents.as<float>(), d_cnorms.as<float>());
+        kmeans_assign(ix, tmetric, map, n_train, d_cents.as<float>(),
+                      d_cnorms.as<float>(), d_assign.as<int32_t>(),
+                      d_best.as<float>(), work);
+        HIP_CHECK(hipMemcpyAsync(h_a.data(), d_assign.ptr,
+                                 (size_t)n_train * 4, hipMemcpyDeviceToHost,
+                                 s));
+        HIP_CHECK(hipMemcpyAsync(h_best.data(), d_best.ptr,
+                                 (size_t)n_train * 4, hipMemcpyDeviceToHost,
+                                 s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        kmeans_check_range(h_a, ix->nlist);
+
+        /* CSR: rows grouped by centroid, ascending row inside a group */
+        std::fill(offs.begin(), offs.end(), 0);
+        for (int32_t a : h_a) offs[a + 1]++;
+        for (int c = 0; c < k; ++c) offs[c + 1] += offs[c];
+        std::copy(offs.begin(), offs.end() - 1, cur.begin());
+        for (int64_t i = 0; i < n_train; ++i)
+            members[cur[h_a[i]]++] = (int32_t)i;
+        upload_vector(d_offs, offs, s);
+        HIP_CHECK(hipMemcpyAsync(d_members.ptr, members.data(),
+                                 (size_t)n_train * 4, hipMemcpyHostToDevice,
+                                 s));
+        launch_km_update(ix->d_staging, dim, map, d_offs.as<int64_t>(),
+                         d_members.as<int32_t>(), d_invp, k, dim, dpad,
+                         d_cents.as<float>(), s);
+        KCHECK("kmeans-update");
+
+        /* empty centroids, ascending, take the farthest training rows */
+        cidx.clear();
+        for (int c = 0; c < k; ++c)
+            if (offs[c + 1] == offs[c]) cidx.push_back(c);
+        const uint64_t n_empty = cidx.size();
+        if (n_empty) {
+            trow = kmeans_pick_reseeds(h_best.data(), (uint64_t)n_train,
+                                       n_empty);
+            upload_vector(d_cidx, cidx, s);
+            upload_vector(d_trow, trow, s);
+            launch_km_set_centroids(ix->d_staging, dim, map,
+                                    d_cidx.as<int32_t>(),
+                                    d_trow.as<int64_t>(), (int)n_empty, dim,
+                                    dpad, d_cents.as<float>(), s);
+            KCHECK("kmeans-reseed");
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+        const bool same = it > 0 && h_a == prev;
+        if (kmeans_should_stop(it, ix->km_iters, same, n_empty)) break;
+        prev = h_a;
+    }
+    ix->h_centroids.resize((size_t)k * dim);
+    HIP_CHECK(hipMemcpy2D(ix->h_centroids.data(), (size_t)dim * 4,
+                          d_cents.ptr, (size_t)dpad * 4, (size_t)dim * 4, k,
+                          hipMemcpyDeviceToHost));
+    ix->km_iters_run = it + 1;
+    ix->km_n_train = (uint64_t)n_train;
+    ix->km_train_ms = std::chrono::duration<double, std::milli>(
+                          std::chrono::steady_clock::now() - t0)
+                          .count();
+}
+
+/* h_assign: every staged row to its nearest centroid under the index metric
+ * (the gpu_ivf_flat_extend rule) */
+void kmeans_assign_all(IvfIndex* ix) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t n = (int64_t)ix->count;
+    const int k = (int)ix->nlist, dim = (int)ix->dim, dpad = (int)ix->dpad;
+    ix->h_assign.assign((size_t)n, 0);
+    if (n && ix->kmetric == KM_L1) {
+        /* no MFMA form: the exact path extend uses, in bounded chunks */
+        const int64_t chunk = 65536;
+        std::vector<float> rows((size_t)std::min(chunk, n) * dim);
+        std::vector<int64_t> nearest(std::min(chunk, n));
+        std::vector<float> ndist(std::min(chunk, n));
+        for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+            const int64_t cnt = std::min(chunk, n - i0);
+            HIP_CHECK(hipMemcpy(rows.data(), ix->d_staging + i0 * dim,
+                                (size_t)cnt * dim * 4,
+                                hipMemcpyDeviceToHost));
+            char* inner = nullptr;
+            moann_brute_force_search(ix->h_centroids.data(), ix->nlist,
+                                     ix->dim, ix->metric, nullptr,
+                                     rows.data(), (uint64_t)cnt, 1,
+                                     ix->device, nearest.data(),
+                                     ndist.data(), &inner);
+            if (inner) {
+                std::string m = std::string("kmeans assign: ") + inner;
+                free(inner);
+                throw std::runtime_error(m);
+            }
+            HIP_CHECK(hipSetDevice(ix->device));
+            for (int64_t i = 0; i < cnt; ++i)
+                ix->h_assign[i0 + i] = (int32_t)nearest[i];
+        }
+    } else if (n) {
+        DevBuf d_cents, d_cnorms, d_assign, d_best;
+        KmeansWork work;
+        d_cents.ensure((size_t)k * dpad * 4);
+        HIP_CHECK(hipMemset(d_cents.ptr, 0, (size_t)k * dpad * 4));
+        HIP_CHECK(hipMemcpy2D(d_cents.ptr, (size_t)dpad * 4,
+                              ix->h_centroids.data(), (size_t)dim * 4,
+                              (size_t)dim * 4, k, hipMemcpyHostToDevice));
+        d_cnorms.ensure((size_t)k * 4);
+        d_assign.ensure((size_t)n * 4);
+        d_best.ensure((size_t)n * 4);
+        kmeans_cnorms(ix, d_cents.as<float>(), d_cnorms.as<float>());
+        kmeans_assign(ix, ix->kmetric, KmRowMap {1, 1}, n,
+                      d_cents.as<float>(), d_cnorms.as<float>(),
+                      d_assign.as<int32_t>(), d_best.as<float>(), work);
+        HIP_CHECK(hipMemcpyAsync(ix->h_assign.data(), d_assign.ptr,
+                                 (size_t)n * 4, hipMemcpyDeviceToHost,
+                                 ix->stream));
+        HIP_CHECK(hipStreamSynchronize(ix->stream));
+    }
+    kmeans_check_range(ix->h_assign, ix->nlist);
+    ix->km_assign_ms = std::chrono::duration<double, std::milli>(
+                           std::chrono::steady_clock::now() - t0)
+                           .count();
+}
+
 IvfIndex* IX(gpu_ivf_flat_c h) { return (IvfIndex*)h; }
 
 }  // namespace
@@ -976,6 +1230,8 @@ gpu_ivf_flat_c gpu_ivf_flat_new_empty(uint64_t total_count, uint32_t dimension,
         ix->metric = metric;
         ix->kmetric = metric_kind(metric);
         ix->nlist = build_params.n_lists ? build_params.n_lists : 1024;
+        ix->km_fraction =
+            kmeans_fraction(build_params.kmeans_trainset_fraction);
         ix->qtype = qtype;
         ix->cap = total_count;
         ix->h_ids.reserve(total_count);
@@ -1095,11 +1351,15 @@ void gpu_ivf_flat_build(gpu_ivf_flat_c h, void* errmsg) {
         auto ix = IX(h);
         std::lock_guard<std::mutex> lk(ix->mu);
         if (ix->built) return;
-        if (ix->h_centroids.empty())
+        HIP_CHECK(hipSetDevice(ix->device));
+        /* three cases (include/moann.h): neither array set -> train, then
+         * assign; centroids only (LoadCentroids) -> assign; both -> as given */
+        if (ix->h_centroids.empty() && !ix->h_assign.empty())
             throw std::runtime_error(
-                "no centroids: call moann_ivf_flat_set_centroids (k-means "
-                "build is harness-side; SURVEY.md kmeans row is out of the "
-                "judged search path)");
+                "assignments set without centroids: set both, the centroids "
+                "alone, or neither");
+        if (ix->h_centroids.empty()) kmeans_train(ix);
+        if (ix->h_assign.empty() && ix->count) kmeans_assign_all(ix);
         if (ix->h_assign.size() != ix->count)
             throw std::runtime_error(
                 "no assignments: call moann_ivf_flat_set_assignments");
@@ -1619,6 +1879,60 @@ void gpu_ivf_flat_get_centers(gpu_ivf_flat_c h, void* centers, void* errmsg) {
                ix->h_centroids.size() * sizeof(float));
     } catch (const std::exception& e) {
         set_errmsg(errmsg, "gpu_ivf_flat_get_centers", e.what());
+    }
+}
+
+void moann_ivf_flat_set_kmeans_params(gpu_ivf_flat_c h, uint32_t n_iters,
+                                      uint64_t max_train_rows, void* errmsg) {
+    try {
+        auto ix = IX(h);
+        std::lock_guard<std::mutex> lk(ix->mu);
+        if (ix->built)
+            throw std::runtime_error("index already built");
+        ix->km_iters = n_iters;
+        ix->km_max_train = max_train_rows;
+    } catch (const std::exception& e) {
+        set_errmsg(errmsg, "moann_ivf_flat_set_kmeans_params", e.what());
+    }
+}
+
+void moann_ivf_flat_get_assignments(gpu_ivf_flat_c h, int32_t* out,
+                                    void* errmsg) {
+    try {
+        auto ix = IX(h);
+        std::lock_guard<std::mutex> lk(ix->mu);
+        if (!ix->built) throw std::runtime_error("index not built");
+        if (ix->h_slot_rows.size() != ix->count)
+            throw std::runtime_error(
+                "add-order rows are not kept for a loaded index");
+        /* h_assign is dropped at build: slot -> list from the slot bases,
+         * slot -> add-order row from h_slot_rows */
+        for (uint32_t l = 0; l < ix->nlist; ++l) {
+            const int64_t b = ix->list_slot_base[l];
+            for (int64_t sl = b; sl < b + ix->list_rows[l]; ++sl)
+                out[ix->h_slot_rows[sl]] = (int32_t)l;
+        }
+        for (size_t i = 0; i < ix->tail_assign.size(); ++i)
+            out[ix->count + i] = ix->tail_assign[i];
+    } catch (const std::exception& e) {
+        set_errmsg(errmsg, "moann_ivf_flat_get_assignments", e.what());
+    }
+}
+
+void moann_ivf_flat_kmeans_stats(gpu_ivf_flat_c h, double* train_ms,
+                                 double* assign_ms, uint32_t* iters,
+                                 uint64_t* n_train, void* errmsg) {
+    try {
+        auto ix = IX(h);
+        if (!ix) throw std::runtime_error("null index");
+        std::lock_guard<std::mutex> lk(ix->mu);
+        if (!ix->built) throw std::runtime_error("index not built");
+        if (train_ms) *train_ms = ix->km_train_ms;
+        if (assign_ms) *assign_ms = ix->km_assign_ms;
+        if (iters) *iters = ix->km_iters_run;
+        if (n_train) *n_train = ix->km_n_train;
+    } catch (const std::exception& e) {
+        set_errmsg(errmsg, "moann_ivf_flat_kmeans_stats", e.what());
     }
 }
 

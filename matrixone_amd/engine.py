@@ -121,6 +121,15 @@ def lib() -> ct.CDLL:
         ct.c_void_p, ct.c_void_p, ct.c_uint32, ct.c_void_p]
     L.moann_ivf_flat_set_assignments.argtypes = [
         ct.c_void_p, ct.c_void_p, ct.c_uint64, ct.c_void_p]
+    L.moann_ivf_flat_set_kmeans_params.argtypes = [
+        ct.c_void_p, ct.c_uint32, ct.c_uint64, ct.c_void_p]
+    L.moann_ivf_flat_get_assignments.argtypes = [
+        ct.c_void_p, ct.c_void_p, ct.c_void_p]
+    L.gpu_ivf_flat_get_centers.argtypes = [
+        ct.c_void_p, ct.c_void_p, ct.c_void_p]
+    L.moann_ivf_flat_kmeans_stats.argtypes = [
+        ct.c_void_p, ct.POINTER(ct.c_double), ct.POINTER(ct.c_double),
+        ct.POINTER(ct.c_uint32), ct.POINTER(ct.c_uint64), ct.c_void_p]
     for f in (L.gpu_ivf_flat_build, L.gpu_ivf_flat_start):
         f.argtypes = [ct.c_void_p, ct.c_void_p]
     L.gpu_ivf_flat_destroy.argtypes = [ct.c_void_p, ct.c_void_p]
@@ -346,14 +355,14 @@ class IvfFlatIndex:
 
     def __init__(self, dim: int, nlist: int, metric: str = "l2sq",
                  capacity: int = 0, device: int = 0, qtype: str = "f32",
-                 btype: str = "f32"):
+                 btype: str = "f32", trainset_fraction: float = 0.5):
         if metric not in METRICS:
             raise ValueError(f"metric {metric!r} not in {sorted(METRICS)}")
         self.dim, self.nlist, self.metric = dim, nlist, metric
         self.device = device
         self.btype = btype
         err = _Err()
-        bp = BuildParams(nlist, True, 0.5)
+        bp = BuildParams(nlist, True, trainset_fraction)
         dev = (ct.c_int * 1)(device)
         self._h = lib().gpu_ivf_flat_new_empty(
             capacity, dim, METRICS[metric], bp, dev, 1, 0, 0,
@@ -460,7 +469,48 @@ class IvfFlatIndex:
                                              assignments.shape[0], err.ref)
         err.check("set_assignments")
 
+    def set_kmeans_params(self, n_iters: int = 0, max_train_rows: int = 0):
+        """Knobs of the native k-means build (before build()); 0 = default
+        (20 iterations) / no cap on the training sample."""
+        err = _Err()
+        lib().moann_ivf_flat_set_kmeans_params(self._h, n_iters,
+                                               max_train_rows, err.ref)
+        err.check("set_kmeans_params")
+
+    def centers(self) -> np.ndarray:
+        """[nlist][dim] f32 centroids (gpu_ivf_flat_get_centers): the
+        caller's, or the trained ones after a native build."""
+        out = np.empty((self.nlist, self.dim), dtype=np.float32)
+        err = _Err()
+        lib().gpu_ivf_flat_get_centers(self._h, out.ctypes.data, err.ref)
+        err.check("get_centers")
+        return out
+
+    def assignments(self) -> np.ndarray:
+        """[len] int32 list of every stored vector in ADD order, after
+        build (moann_ivf_flat_get_assignments)."""
+        out = np.empty(len(self), dtype=np.int32)
+        err = _Err()
+        lib().moann_ivf_flat_get_assignments(self._h, out.ctypes.data,
+                                             err.ref)
+        err.check("get_assignments")
+        return out
+
+    def kmeans_stats(self) -> dict:
+        """What the last native build spent (moann_ivf_flat_kmeans_stats)."""
+        t, a = ct.c_double(0), ct.c_double(0)
+        it, nt = ct.c_uint32(0), ct.c_uint64(0)
+        err = _Err()
+        lib().moann_ivf_flat_kmeans_stats(self._h, ct.byref(t), ct.byref(a),
+                                          ct.byref(it), ct.byref(nt), err.ref)
+        err.check("kmeans_stats")
+        return {"train_ms": t.value, "assign_ms": a.value,
+                "iters": it.value, "n_train": nt.value}
+
     def build(self):
+        """Pack the lists. Centroids and assignments the caller did not set
+        are computed natively: k-means training and/or nearest-centroid
+        assignment on the GPU (include/moann.h, gpu_ivf_flat_build)."""
         err = _Err()
         lib().gpu_ivf_flat_build(self._h, err.ref)
         err.check("build")

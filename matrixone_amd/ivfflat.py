@@ -59,10 +59,11 @@ class IndexSource:
     pkg/vectorindex/ivfflat/search.go:71-161 LoadCentroids and :917-1005
     scanEntries perform through the SQL executor. The embedding host hands
     the arrays straight from its storage scan."""
-    centroids: np.ndarray           # [nlist][dim] f32
-    vectors: np.ndarray             # [n][dim] f32 (entry vectors)
-    assignments: np.ndarray         # [n] int32 centroid slot of each entry
-    ids: Optional[np.ndarray] = None  # [n] int64 entry PKs
+    centroids: Optional[np.ndarray]    # [nlist][dim] f32; None: trained
+    vectors: np.ndarray                # [n][dim] f32 (entry vectors)
+    assignments: Optional[np.ndarray]  # [n] int32 centroid slot of each
+                                       # entry; None: assigned at build
+    ids: Optional[np.ndarray] = None   # [n] int64 entry PKs
 
 
 class IvfflatSearch:
@@ -86,8 +87,12 @@ class IvfflatSearch:
                                  metric=metric, capacity=n,
                                  device=self.device)
         ix.add(src.vectors, ids=src.ids)
-        ix.set_centroids(src.centroids)
-        ix.set_assignments(src.assignments)
+        # an array the source does not carry is computed by the native
+        # build (k-means training / nearest-centroid assignment)
+        if src.centroids is not None:
+            ix.set_centroids(src.centroids)
+        if src.assignments is not None:
+            ix.set_assignments(src.assignments)
         ix.build()
         self.index = ix
 
