@@ -196,8 +196,11 @@ __global__ __launch_bounds__(1024) void hnsw_search_kernel(
     __syncthreads();
     const uint64_t slot_mask = FILTERED ? FSLOT_MASK : SLOT_MASK;
 
-    const int max_expansions = 16 * efc + 64; /* bounded spin (guide rule) */
-    for (int it = 0; it < max_expansions; ++it) {
+    /* bounded spin (guide rule): `visited` gates insertion, so a slot enters
+     * the list — and is expanded — at most once; n expansions cannot bind on
+     * a valid graph. usearch has no bound here, and a smaller one (16*efc+64
+     * once) cut level-0 paths longer than it short of the query. */
+    for (int64_t it = 0; it < n; ++it) {
         const int sz = sc[0];
         /* FILTERED: passing count + the ef-th passing dist (= radius).
          * contiguous per-thread blocks so thread 0 can localise the ef-th. */
