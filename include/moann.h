@@ -535,6 +535,87 @@ typedef struct {
 void moann_ivf_flat_perf(gpu_ivf_flat_c index_c, moann_perf_t* out);
 void moann_ivf_flat_perf_reset(gpu_ivf_flat_c index_c);
 
+/* --- resident brute force (moann extension) ----------------- */
+
+/* Exact top-k over a dataset that STAYS in HBM, with appends, soft deletes
+ * and a row filter — what moann_brute_force_search rebuilds on every call.
+ * Every entry is a moann extension (no gpu_brute_force_* name is claimed)
+ * and follows the errmsg convention above.
+ *
+ * Storage   f32 rows, row-major [cap][dpad] in HBM, zero-padded, with
+ *           dpad = (dim+3)&~3 (the rule of the IVF centroid matrix); per row
+ *           also |x|^2 (f32), the int64 id and one bit of an alive bitset.
+ * add       works at any time, also between searches. Capacity grows by
+ *           doubling with a device-to-device copy; nothing is re-packed. At
+ *           most 2^31-1 rows; more is an error. ids = NULL numbers the rows
+ *           sequentially from len.
+ * Metrics   L2Expanded, L2SqrtExpanded, InnerProduct, CosineExpanded. L1 has
+ *           no GEMM form: moann_bf_new refuses it and points to
+ *           moann_brute_force_search.
+ * Distances those of the MFMA rank GEMM, from f32 norms: L2 = |q|^2 + |x|^2
+ *           - 2 x.q clamped at 0 (the expanded form, so its rounding differs
+ *           from the one-shot entry's difference form); IP = -x.q (MO
+ *           convention, as in every moann_* entry); cosine = 1 - x.q/(|x||q|)
+ *           clamped, 1 for a zero vector; L2sqrt takes the square root after
+ *           the selection.
+ * Results   dense [nq][k], ascending by (distance, row index): equal
+ *           distances resolve to the row added first. (-1, FLT_MAX) padding
+ *           when fewer than k rows survive. A distance that is not below
+ *           FLT_MAX (overflow, NaN) is reported as padding. The fused
+ *           kernel keeps the (distance, row) order among EQUAL distances
+ *           always; launch_topk keeps it while it selects among at most 1024
+ *           candidates: slices * k in the final selection of
+ *           either mode, and the rows of a distance tile in gemm mode.
+ *           Beyond that the distances returned are still exact and sorted,
+ *           and which of several bit-equal rows fill the last ranks is not
+ *           specified.
+ * Filter    row_bitset: one bit per row in add order, LSB-first u32 words; a
+ *           CLEARED bit excludes the row (moann_ivf_flat_search_filtered's
+ *           polarity); nbits must cover len. Deleted rows are excluded in
+ *           every search (delete is soft: the row keeps its place and
+ *           moann_bf_len counts it; an unknown id is a no-op). The kernels
+ *           see alive AND filter as one bitset.
+ * Limits    k in [1, 4096]; nq = 0 returns at once.
+ * Modes     moann_bf_set_params: mode 0 = auto (fused for k <=
+ *           moann_bf_fused_kmax() on at least 30 000 rows and 4 000 000
+ *           row-query pairs, where it was measured faster; else gemm),
+ *           1 = fused MFMA distance +
+ *           top-k kernel, 2 = gemm (rank GEMM into a distance tile, then a
+ *           top-k per tile: the composition that serves every k).
+ *           slice_rows = 0 lets the planner cut the rows; another value must
+ *           be a multiple of the 128-row tile and is the rows per slice
+ *           (fused) or per distance tile (gemm).
+ * Perf      scan_ms = the fused kernel, or in gemm mode the per-tile loop
+ *           (GEMM, filter, per-tile top-k); select_ms = final top-k + gather;
+ *           other_ms = the rest of the call's wall time. */
+typedef void* moann_bf_c;
+
+moann_bf_c moann_bf_new(uint32_t dimension, distance_type_t metric,
+                        uint64_t capacity_hint, const int* devices,
+                        int device_count, void* errmsg);
+void moann_bf_add(moann_bf_c h, const float* rows, uint64_t n,
+                  const int64_t* ids, void* errmsg);
+void moann_bf_delete_id(moann_bf_c h, int64_t id, void* errmsg);
+void moann_bf_set_params(moann_bf_c h, uint32_t mode, uint32_t slice_rows,
+                         void* errmsg);
+/* out_ids [nq][k] int64 and out_dists [nq][k] f32 are caller (host) buffers */
+void moann_bf_search(moann_bf_c h, const float* queries, uint64_t nq,
+                     uint32_t dim, uint32_t k, int64_t* out_ids,
+                     float* out_dists, void* errmsg);
+/* queries_dev: contiguous f32 [nq][dim] in device memory, producer synced */
+void moann_bf_search_device(moann_bf_c h, const void* queries_dev, uint64_t nq,
+                            uint32_t dim, uint32_t k, int64_t* out_ids,
+                            float* out_dists, void* errmsg);
+void moann_bf_search_filtered(moann_bf_c h, const float* queries, uint64_t nq,
+                              uint32_t dim, uint32_t k,
+                              const uint32_t* row_bitset, uint64_t nbits,
+                              int64_t* out_ids, float* out_dists,
+                              void* errmsg);
+uint64_t moann_bf_len(moann_bf_c h);  /* rows added, deleted ones included */
+uint32_t moann_bf_fused_kmax(void);   /* largest k the fused kernel serves */
+void moann_bf_perf(moann_bf_c h, moann_perf_t* out);
+void moann_bf_destroy(moann_bf_c h, void* errmsg);
+
 /* --- IVF-PQ (cgo/cuvs/ivf_pq_c.h precedent) -------------- */
 
 /* ADC search over per-subspace codebooks with coarse-residual encoding (the

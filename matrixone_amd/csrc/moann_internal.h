@@ -137,6 +137,38 @@ void launch_km_gather_pad(const float* rows, int64_t row_stride, KmRowMap map,
                           int64_t i0, int64_t count, int dim, int dpad,
                           float* out, hipStream_t stream);
 
+/* ---- resident brute-force index (bf_kernels.hip) ----
+ * The candidate buffer of a search is [nq][slices][k] (distance, row) pairs,
+ * each slice's segment sorted ascending by (distance, row) and padded with
+ * (FLT_MAX, -1); rows are indices into the row store. `mask` has one bit per
+ * row, cleared = excluded, null = every row passes. */
+struct BfPlan; /* moann_bf_plan.h */
+
+/* Fused exact distance + per-slice top-k for KM_L2SQ, KM_IP and KM_COS
+ * (rank_gemm_kernel's distances from the given norms), k <= BF_FUSED_KMAX:
+ * fills the whole candidate buffer of `plan` (slices, tiles_per_slice) for
+ * these nq queries. Deterministic; throws std::logic_error for KM_L1 or a
+ * larger k. */
+void launch_bf_fused_topk(int metric, const float* rows, const float* xnorms,
+                          const uint32_t* mask, int64_t n,
+                          const float* queries, const float* qnorms, int nq,
+                          int dpad, int k, const BfPlan& plan, float* cand_d,
+                          int32_t* cand_r, hipStream_t stream);
+/* dmat [nq][len] holds rows [row0, row0+len): excluded rows -> FLT_MAX */
+void launch_bf_mask(float* dmat, int nq, int64_t len, int64_t row0,
+                    const uint32_t* mask, hipStream_t stream);
+/* one chunk's launch_topk output [nq][k] -> segment `slice` of the candidate
+ * buffer; slots that are padding or carry FLT_MAX become (FLT_MAX, -1) */
+void launch_bf_stash(const int32_t* sel_slots, const float* sel_dists, int nq,
+                     int k, int64_t row0, int64_t slice, int64_t nslices,
+                     float* cand_d, int32_t* cand_r, hipStream_t stream);
+/* final launch_topk slots -> candidate row -> id; (-1, FLT_MAX) for padding;
+ * do_sqrt takes the square root of the selected distances (L2sqrt) */
+void launch_bf_gather(const int32_t* sel_slots, const float* sel_dists,
+                      const int32_t* cand_r, int64_t cand_per_q,
+                      const int64_t* ids, int nq, int k, int do_sqrt,
+                      int64_t* out_ids, float* out_dists, hipStream_t stream);
+
 /* Quantized (int8/uint8) list scan + helpers. `layout` is the byte order of
  * `packed` (moann_scan_plan.h): ROWS16 takes the variant's dot or uchar4
  * kernel, MFMA64 takes scan_i8_mfma_kernel and throws for a variant, metric

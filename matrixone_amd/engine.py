@@ -230,6 +230,25 @@ def lib() -> ct.CDLL:
     L.moann_pairwise_distance.argtypes = [
         ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_uint64, ct.c_uint32,
         ct.c_int, ct.c_void_p, ct.c_void_p]
+    L.moann_bf_new.restype = ct.c_void_p
+    L.moann_bf_new.argtypes = [ct.c_uint32, ct.c_int, ct.c_uint64,
+                               ct.c_void_p, ct.c_int, ct.c_void_p]
+    L.moann_bf_add.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint64,
+                               ct.c_void_p, ct.c_void_p]
+    L.moann_bf_delete_id.argtypes = [ct.c_void_p, ct.c_int64, ct.c_void_p]
+    L.moann_bf_set_params.argtypes = [ct.c_void_p, ct.c_uint32, ct.c_uint32,
+                                      ct.c_void_p]
+    for f in (L.moann_bf_search, L.moann_bf_search_device):
+        f.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint64, ct.c_uint32,
+                      ct.c_uint32, ct.c_void_p, ct.c_void_p, ct.c_void_p]
+    L.moann_bf_search_filtered.argtypes = [
+        ct.c_void_p, ct.c_void_p, ct.c_uint64, ct.c_uint32, ct.c_uint32,
+        ct.c_void_p, ct.c_uint64, ct.c_void_p, ct.c_void_p, ct.c_void_p]
+    L.moann_bf_len.restype = ct.c_uint64
+    L.moann_bf_len.argtypes = [ct.c_void_p]
+    L.moann_bf_fused_kmax.restype = ct.c_uint32
+    L.moann_bf_perf.argtypes = [ct.c_void_p, ct.POINTER(PerfT)]
+    L.moann_bf_destroy.argtypes = [ct.c_void_p, ct.c_void_p]
     L.moann_device_count.restype = ct.c_int
     L.moann_version.restype = ct.c_char_p
     _lib = L
@@ -754,18 +773,29 @@ def pairwise_distance(metric: str, query, rows, device: int = 0):
 
 
 def search_with_tail(index, queries, k: int, nprobe: int,
-                     tail_vecs, tail_ids, metric: str = None):
+                     tail_vecs, tail_ids, metric: str = None,
+                     tail_index=None):
     """CDC-tail overflow search (ivfpq/search_gpu.go:222-428 shape): the
     built index covers the snapshot; rows appended since (the CDC tail,
     not yet merged into the index) are brute-forced and the two top-k
     blocks are merged with cpu_topk_merge_sharded semantics (skip -1,
-    dense ascending, (-1, FLT_MAX) padding)."""
+    dense ascending, (-1, FLT_MAX) padding).
+
+    tail_index: a BruteForceIndex that already holds the tail (rows and ids
+    appended as they arrived); it is searched in place of brute-forcing
+    tail_vecs, which are then not looked at."""
     metric = metric or getattr(index, "metric", "l2sq")
     main_ids, main_d = index.search(queries, k, nprobe)
-    if tail_vecs is None or len(tail_vecs) == 0:
+    if tail_index is not None:
+        if len(tail_index) == 0:
+            return main_ids, main_d
+        t_ids, t_d = tail_index.search(queries, min(k, len(tail_index)))
+    elif tail_vecs is None or len(tail_vecs) == 0:
         return main_ids, main_d
-    t_ids, t_d = brute_force_search(tail_vecs, queries, min(k, len(tail_vecs)),
-                                    metric=metric, ids=tail_ids)
+    else:
+        t_ids, t_d = brute_force_search(tail_vecs, queries,
+                                        min(k, len(tail_vecs)),
+                                        metric=metric, ids=tail_ids)
     nq = main_ids.shape[0]
     kk = t_ids.shape[1]
     if kk < k:  # pad the tail block to k for a uniform merge
@@ -806,6 +836,114 @@ def brute_force_search(dataset, queries, k: int, metric: str = "l2sq",
         out_ids.ctypes.data, out_dists.ctypes.data, err.ref)
     err.check("brute_force_search")
     return out_ids, out_dists
+
+
+BF_MODES = {"auto": 0, "fused": 1, "gemm": 2}
+
+
+def bf_fused_kmax() -> int:
+    """Largest k the fused brute-force kernel serves."""
+    return int(lib().moann_bf_fused_kmax())
+
+
+class BruteForceIndex:
+    """Resident exact index (moann_bf_*, include/moann.h): the f32 rows stay
+    in HBM; add() appends at any time, delete() is soft, search() returns
+    [nq][k] ascending by (distance, row added first), (-1, FLT_MAX) padded.
+    Metrics l2sq, l2, ip (MO convention -a.b) and cos; l1 is refused."""
+
+    def __init__(self, dim: int, metric: str = "l2sq", capacity: int = 0,
+                 device: int = 0):
+        self.dim, self.metric = int(dim), metric
+        err = _Err()
+        devs = (ct.c_int * 1)(device)
+        self._h = lib().moann_bf_new(self.dim, METRICS[metric], capacity,
+                                     devs, 1, err.ref)
+        err.check("BruteForceIndex")
+        if not self._h:
+            raise MoannError("BruteForceIndex: moann_bf_new returned NULL")
+
+    def add(self, rows, ids=None):
+        rows = _as_f32(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise MoannError(f"add: rows must be [n][{self.dim}]")
+        idp = None
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            if ids.shape != (rows.shape[0],):
+                raise MoannError("add: one id per row")
+            idp = ids.ctypes.data
+        err = _Err()
+        lib().moann_bf_add(self._h, rows.ctypes.data, rows.shape[0], idp,
+                           err.ref)
+        err.check("add")
+
+    def delete(self, id_: int):
+        err = _Err()
+        lib().moann_bf_delete_id(self._h, int(id_), err.ref)
+        err.check("delete")
+
+    def set_params(self, mode="auto", slice_rows: int = 0):
+        """mode: "auto", "fused" or "gemm"; slice_rows: 0 = planner, else a
+        multiple of the 128-row tile."""
+        err = _Err()
+        lib().moann_bf_set_params(self._h, BF_MODES.get(mode, mode),
+                                  slice_rows, err.ref)
+        err.check("set_params")
+
+    def search(self, queries, k: int, row_bitset=None):
+        """row_bitset: u32 words, one bit per row in add order, a cleared bit
+        excludes the row; it must cover len(self)."""
+        queries = _as_f32(queries)
+        nq = queries.shape[0]
+        out_ids = np.empty((nq, max(k, 0)), dtype=np.int64)
+        out_dists = np.empty((nq, max(k, 0)), dtype=np.float32)
+        err = _Err()
+        if row_bitset is None:
+            lib().moann_bf_search(self._h, queries.ctypes.data, nq,
+                                  queries.shape[1], k, out_ids.ctypes.data,
+                                  out_dists.ctypes.data, err.ref)
+        else:
+            row_bitset = np.ascontiguousarray(row_bitset, dtype=np.uint32)
+            lib().moann_bf_search_filtered(
+                self._h, queries.ctypes.data, nq, queries.shape[1], k,
+                row_bitset.ctypes.data, row_bitset.size * 32,
+                out_ids.ctypes.data, out_dists.ctypes.data, err.ref)
+        err.check("search")
+        return out_ids, out_dists
+
+    def search_device(self, queries_tensor, k: int):
+        """queries_tensor: a contiguous f32 torch CUDA tensor [nq][dim]; the
+        caller must have synchronised the producing stream."""
+        nq, qdim = queries_tensor.shape
+        out_ids = np.empty((nq, k), dtype=np.int64)
+        out_dists = np.empty((nq, k), dtype=np.float32)
+        err = _Err()
+        lib().moann_bf_search_device(
+            self._h, ct.c_void_p(queries_tensor.data_ptr()), nq, qdim, k,
+            out_ids.ctypes.data, out_dists.ctypes.data, err.ref)
+        err.check("search_device")
+        return out_ids, out_dists
+
+    def __len__(self):
+        return int(lib().moann_bf_len(self._h))
+
+    def perf(self) -> dict:
+        p = PerfT()
+        lib().moann_bf_perf(self._h, ct.byref(p))
+        return {f[0]: getattr(p, f[0]) for f in PerfT._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            err = _Err()
+            lib().moann_bf_destroy(self._h, err.ref)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class IvfPqIndex:
