@@ -545,6 +545,11 @@ void moann_ivf_flat_perf_reset(gpu_ivf_flat_c index_c);
  * Storage   f32 rows, row-major [cap][dpad] in HBM, zero-padded, with
  *           dpad = (dim+3)&~3 (the rule of the IVF centroid matrix); per row
  *           also |x|^2 (f32), the int64 id and one bit of an alive bitset.
+ *           moann_bf_new_typed(Quantization_F16) stores IEEE binary16 rows
+ *           instead, [cap][dpad_h] with dpad_h = (dim+7)&~7 (every row starts
+ *           on 16 bytes): half the bytes per row, and the fused kernel runs
+ *           on the f16 MFMA. Quantization_F32 is moann_bf_new; every other
+ *           type is an error. See "F16 store" below.
  * add       works at any time, also between searches. Capacity grows by
  *           doubling with a device-to-device copy; nothing is re-packed. At
  *           most 2^31-1 rows; more is an error. ids = NULL numbers the rows
@@ -585,6 +590,30 @@ void moann_ivf_flat_perf_reset(gpu_ivf_flat_c index_c);
  *           slice_rows = 0 lets the planner cut the rows; another value must
  *           be a multiple of the 128-row tile and is the rows per slice
  *           (fused) or per distance tile (gemm).
+ * F16 store An F16 index answers the question for the ROUNDED data: it is
+ *           exact with respect to what it stores. moann_bf_add narrows its
+ *           f32 rows with round-to-nearest-even; moann_bf_add_half takes
+ *           binary16 rows as they are (F16 indexes only; an error on an F32
+ *           index). A coordinate without a finite f16 value (|v| >= 65520,
+ *           which rounds to infinity, an infinity or a NaN, in either entry)
+ *           fails the add with an error that names the first such row; the
+ *           failed add stores nothing and moann_bf_len is unchanged. Queries
+ *           stay f32 in all three search entries and are narrowed the same
+ *           way; a host query outside the f16 range is an error before any
+ *           launch. For moann_bf_search_device the CALLER guarantees the
+ *           range: a non-finite distance is then reported as padding (see
+ *           Results). Distances are those of the rounded operands: the dot
+ *           product from the f16 MFMA (exact products, f32 accumulation),
+ *           |x|^2 and |q|^2 in f32 from the rounded values, then the
+ *           formulas above. The gemm mode widens a slice of rows to an f32
+ *           tile (at most 256 MiB, which bounds slice_rows in that mode) and
+ *           runs the same chain over the rounded queries widened back, so
+ *           both modes answer the same question. Append, delete, filter, the
+ *           tie rule, the k limits and moann_bf_set_params are those of the
+ *           F32 index; mode auto keeps the 30 000-row bound and takes
+ *           the fused kernel from 1 000 000 row-query pairs on, where it
+ *           was measured faster than this store's gemm mode. scan_bytes
+ *           counts 2 bytes per element.
  * Perf      scan_ms = the fused kernel, or in gemm mode the per-tile loop
  *           (GEMM, filter, per-tile top-k); select_ms = final top-k + gather;
  *           other_ms = the rest of the call's wall time. */
@@ -593,8 +622,16 @@ typedef void* moann_bf_c;
 moann_bf_c moann_bf_new(uint32_t dimension, distance_type_t metric,
                         uint64_t capacity_hint, const int* devices,
                         int device_count, void* errmsg);
+/* storage: Quantization_F32 (exactly moann_bf_new) or Quantization_F16 */
+moann_bf_c moann_bf_new_typed(uint32_t dimension, distance_type_t metric,
+                              quantization_t storage, uint64_t capacity_hint,
+                              const int* devices, int device_count,
+                              void* errmsg);
 void moann_bf_add(moann_bf_c h, const float* rows, uint64_t n,
                   const int64_t* ids, void* errmsg);
+/* rows: IEEE binary16, row-major [n][dim], host memory; F16 indexes only */
+void moann_bf_add_half(moann_bf_c h, const uint16_t* rows, uint64_t n,
+                       const int64_t* ids, void* errmsg);
 void moann_bf_delete_id(moann_bf_c h, int64_t id, void* errmsg);
 void moann_bf_set_params(moann_bf_c h, uint32_t mode, uint32_t slice_rows,
                          void* errmsg);
@@ -612,6 +649,7 @@ void moann_bf_search_filtered(moann_bf_c h, const float* queries, uint64_t nq,
                               int64_t* out_ids, float* out_dists,
                               void* errmsg);
 uint64_t moann_bf_len(moann_bf_c h);  /* rows added, deleted ones included */
+uint32_t moann_bf_storage(moann_bf_c h); /* the handle's quantization_t */
 uint32_t moann_bf_fused_kmax(void);   /* largest k the fused kernel serves */
 void moann_bf_perf(moann_bf_c h, moann_perf_t* out);
 void moann_bf_destroy(moann_bf_c h, void* errmsg);

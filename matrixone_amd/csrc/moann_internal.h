@@ -154,6 +154,19 @@ void launch_bf_fused_topk(int metric, const float* rows, const float* xnorms,
                           const float* queries, const float* qnorms, int nq,
                           int dpad, int k, const BfPlan& plan, float* cand_d,
                           int32_t* cand_r, hipStream_t stream);
+/* The same over an f16 row store (bf_half_kernels.hip): rows and queries are
+ * binary16 [.][dpad], dpad % 8 == 0, zero-padded; the dot product comes from
+ * the f16 MFMA (exact products, f32 accumulation), the norms are f32. */
+void launch_bf_fused_topk_h(int metric, const uint16_t* rows,
+                            const float* xnorms, const uint32_t* mask,
+                            int64_t n, const uint16_t* queries,
+                            const float* qnorms, int nq, int dpad, int k,
+                            const BfPlan& plan, float* cand_d, int32_t* cand_r,
+                            hipStream_t stream);
+/* binary16 [nrows][dpad_h] -> f32 [nrows][dpad_w] (dpad_w <= dpad_h), exact:
+ * the gemm mode's operand over an f16 store */
+void launch_bf_widen_half(const uint16_t* in, int64_t nrows, int dpad_h,
+                          int dpad_w, float* out, hipStream_t stream);
 /* dmat [nq][len] holds rows [row0, row0+len): excluded rows -> FLT_MAX */
 void launch_bf_mask(float* dmat, int nq, int64_t len, int64_t row0,
                     const uint32_t* mask, hipStream_t stream);

@@ -233,6 +233,14 @@ def lib() -> ct.CDLL:
     L.moann_bf_new.restype = ct.c_void_p
     L.moann_bf_new.argtypes = [ct.c_uint32, ct.c_int, ct.c_uint64,
                                ct.c_void_p, ct.c_int, ct.c_void_p]
+    L.moann_bf_new_typed.restype = ct.c_void_p
+    L.moann_bf_new_typed.argtypes = [ct.c_uint32, ct.c_int, ct.c_int,
+                                     ct.c_uint64, ct.c_void_p, ct.c_int,
+                                     ct.c_void_p]
+    L.moann_bf_add_half.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint64,
+                                    ct.c_void_p, ct.c_void_p]
+    L.moann_bf_storage.restype = ct.c_uint32
+    L.moann_bf_storage.argtypes = [ct.c_void_p]
     L.moann_bf_add.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_uint64,
                                ct.c_void_p, ct.c_void_p]
     L.moann_bf_delete_id.argtypes = [ct.c_void_p, ct.c_int64, ct.c_void_p]
@@ -839,6 +847,7 @@ def brute_force_search(dataset, queries, k: int, metric: str = "l2sq",
 
 
 BF_MODES = {"auto": 0, "fused": 1, "gemm": 2}
+BF_STORAGES = {"f32": 0, "f16": 1}  # quantization_t; the two the index stores
 
 
 def bf_fused_kmax() -> int:
@@ -847,24 +856,48 @@ def bf_fused_kmax() -> int:
 
 
 class BruteForceIndex:
-    """Resident exact index (moann_bf_*, include/moann.h): the f32 rows stay
-    in HBM; add() appends at any time, delete() is soft, search() returns
+    """Resident exact index (moann_bf_*, include/moann.h): the rows stay in
+    HBM; add() appends at any time, delete() is soft, search() returns
     [nq][k] ascending by (distance, row added first), (-1, FLT_MAX) padded.
-    Metrics l2sq, l2, ip (MO convention -a.b) and cos; l1 is refused."""
+    Metrics l2sq, l2, ip (MO convention -a.b) and cos; l1 is refused.
+
+    storage: "f32", or "f16" for binary16 rows (half the bytes, the fused
+    kernel on the f16 MFMA). An f16 index rounds what it is given to nearest
+    even, answers exactly for the rounded rows and queries, and refuses
+    values outside the finite f16 range."""
 
     def __init__(self, dim: int, metric: str = "l2sq", capacity: int = 0,
-                 device: int = 0):
+                 storage: str = "f32", device: int = 0):
         self.dim, self.metric = int(dim), metric
         err = _Err()
         devs = (ct.c_int * 1)(device)
-        self._h = lib().moann_bf_new(self.dim, METRICS[metric], capacity,
-                                     devs, 1, err.ref)
+        if storage == "f32":
+            self._h = lib().moann_bf_new(self.dim, METRICS[metric], capacity,
+                                         devs, 1, err.ref)
+        else:
+            # a type the index does not store goes to the library as it is,
+            # whose error names the two it does
+            q = BF_STORAGES.get(storage, IvfFlatIndex.QTYPES.get(storage))
+            if q is None:
+                raise MoannError(f"BruteForceIndex: storage {storage!r} must "
+                                 "be 'f32' or 'f16'")
+            self._h = lib().moann_bf_new_typed(self.dim, METRICS[metric], q,
+                                               capacity, devs, 1, err.ref)
         err.check("BruteForceIndex")
         if not self._h:
             raise MoannError("BruteForceIndex: moann_bf_new returned NULL")
 
+    @property
+    def storage(self) -> str:
+        q = int(lib().moann_bf_storage(self._h))
+        return next(name for name, v in BF_STORAGES.items() if v == q)
+
     def add(self, rows, ids=None):
-        rows = _as_f32(rows)
+        """rows [n][dim]. On an f16 index a float16 array is stored as it is
+        (moann_bf_add_half); anything else goes as f32 and is narrowed."""
+        as_half = (self.storage == "f16" and
+                   getattr(rows, "dtype", None) == np.float16)
+        rows = np.ascontiguousarray(rows) if as_half else _as_f32(rows)
         if rows.ndim != 2 or rows.shape[1] != self.dim:
             raise MoannError(f"add: rows must be [n][{self.dim}]")
         idp = None
@@ -874,9 +907,26 @@ class BruteForceIndex:
                 raise MoannError("add: one id per row")
             idp = ids.ctypes.data
         err = _Err()
-        lib().moann_bf_add(self._h, rows.ctypes.data, rows.shape[0], idp,
-                           err.ref)
+        entry = lib().moann_bf_add_half if as_half else lib().moann_bf_add
+        entry(self._h, rows.ctypes.data, rows.shape[0], idp, err.ref)
         err.check("add")
+
+    def add_half(self, rows, ids=None):
+        """moann_bf_add_half whatever the index stores: float16 rows [n][dim]
+        as they are; an error on an f32 index."""
+        rows = np.ascontiguousarray(rows, dtype=np.float16)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise MoannError(f"add_half: rows must be [n][{self.dim}]")
+        idp = None
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            if ids.shape != (rows.shape[0],):
+                raise MoannError("add_half: one id per row")
+            idp = ids.ctypes.data
+        err = _Err()
+        lib().moann_bf_add_half(self._h, rows.ctypes.data, rows.shape[0], idp,
+                                err.ref)
+        err.check("add_half")
 
     def delete(self, id_: int):
         err = _Err()

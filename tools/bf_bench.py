@@ -9,6 +9,10 @@ replaces for repeated searches, on the same rows and queries:
            index, scans it and destroys it — timed whole, because that is
            what a caller pays per search today
 
+`--storage f16` builds the resident index over an f16 row store (the fused
+kernel on the f16 MFMA, gemm over a widened slice); the default f32 prints
+what it always printed.
+
 Shapes (rows x dim, nq, k): the batch shape 1M x 768 / 1024 / 10, the CDC
 tail shape 10 000 x 768 / 1024 / 10, and the small batches nq 1 and nq 16 at
 1M x 768. Per shape one warm-up search per mode, then `--runs` rounds that
@@ -51,6 +55,8 @@ def main():
     ap.add_argument("--k", type=int, default=0, help="override every shape's k")
     ap.add_argument("--shape", action="append", default=[],
                     help="extra shape NAME=ROWS,DIM,NQ,K; replaces --shapes")
+    ap.add_argument("--storage", default="f32", choices=["f32", "f16"],
+                    help="row store of the resident index (oneshot stays f32)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     if args.shape:
@@ -97,7 +103,8 @@ def main():
         X = rows_of(n, dim)
         Q = np.random.default_rng(3).standard_normal((nq, dim)).astype(
             np.float32)
-        ix = engine.BruteForceIndex(dim, metric="l2sq", capacity=n)
+        ix = engine.BruteForceIndex(dim, metric="l2sq", capacity=n,
+                                    storage=args.storage)
         t0 = time.perf_counter()
         ix.add(X)
         add_ms = (time.perf_counter() - t0) * 1e3
@@ -131,12 +138,16 @@ def main():
                 wall, perf, _, _ = run(mode)
                 res = {"shape": name, "rows": n, "dim": dim, "nq": nq, "k": k,
                        "mode": mode, "round": r, "wall_ms": round(wall, 3)}
+                if args.storage != "f32":  # f32 lines stay as they were
+                    res["storage"] = args.storage
                 if perf:
                     res.update({f: round(v, 3) for f, v in perf.items()})
                 results.append(res)
                 emit(res)
         ix.close()
         summary[name] = {"add_ms": round(add_ms, 1), "id_agreement": agree}
+        if args.storage != "f32":
+            summary[name]["storage"] = args.storage
         for mode in modes:
             rs = [x for x in results if x["mode"] == mode]
             summary[name][mode] = {
