@@ -327,6 +327,45 @@ uint64_t gpu_ivf_flat_search_quantize_async(
 void moann_ivf_flat_enable_refine(gpu_ivf_flat_c index_c, uint32_t depth,
                                   void* errmsg);
 
+/* moann extension — the per-query selection over the candidate buffer and
+ * the tail of the two-stage scan. Default: long rows are selected in one
+ * read against a sampled threshold, and the exact re-rank, final top-k, id
+ * gather and score transform of the refine path run as one kernel (refine
+ * depth <= 1024). legacy != 0 restores the radix select and the four-kernel
+ * tail; results are the same either way. An index starts legacy when
+ * MOANN_REFINE_TAIL=legacy is set in the environment. */
+void moann_ivf_flat_set_refine_tail(gpu_ivf_flat_c index_c, int legacy,
+                                    void* errmsg);
+
+/* moann extension — queries whose selection the threshold filter finished,
+ * and queries it handed back to the radix select (threshold too low or too
+ * high), counted over the life of the index. Waits for submitted searches.
+ * Either out pointer may be null. */
+void moann_ivf_flat_select_stats(gpu_ivf_flat_c index_c, uint64_t* filtered,
+                                 uint64_t* fallback, void* errmsg);
+
+/* moann extension — the selection kernels alone, host arrays in and out:
+ * row q is dists[qoffs[q], qoffs[q+1]); out_slots/out_dists [nq][k] get its
+ * k smallest by (distance key, position), ascending, (-1, FLT_MAX) padded.
+ * mode 0: radix select; mode 1: threshold filter with its radix fallback.
+ * fallbacks: rows of this call that fell back (mode 1); kernel_ms: device
+ * time of the one launch. Both may be null. k <= 4096. */
+void moann_select_topk(const float* dists, const int64_t* qoffs, int64_t nq,
+                       int32_t k, int32_t mode, int32_t* out_slots,
+                       float* out_dists, uint64_t* fallbacks,
+                       double* kernel_ms, void* errmsg);
+
+/* moann extension — the filter's rule for a row of `count` values at this k
+ * (moann_select_plan.h): whether it takes the filter path, the number of
+ * sampled keys, the rank of the sample that becomes the threshold, and the
+ * rule's constants. moann_select_sample_positions writes the `sample` row
+ * positions that are read (nothing when the row does not take the filter
+ * path). Pure host arithmetic; any out pointer of the first may be null. */
+void moann_select_plan(int64_t count, int32_t k, int32_t* filter,
+                       int32_t* sample, int32_t* rank, int32_t* capacity,
+                       int64_t* min_count, int32_t* kmax);
+void moann_select_sample_positions(int64_t count, int32_t k, int64_t* out);
+
 /* moann extension — pipelined batch submit/wait. Submit runs the centroid
  * rank and the host job build immediately and enqueues the list scan and
  * result readback without waiting; a second submit overlaps its rank/build

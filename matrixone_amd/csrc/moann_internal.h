@@ -60,6 +60,17 @@ void launch_topk(const float* dists, const int64_t* qoffs, int64_t uniform_n,
                  int nq, int k, int32_t* out_slots, float* out_dists,
                  hipStream_t stream);
 
+/* The same selection for long ragged rows (qoffs required, dists 16-byte
+ * aligned): rows the rule of moann_select_plan.h admits are selected in one
+ * read against a sampled threshold (select_filter_kernel), every other row,
+ * and a row whose threshold turns out bad, by the radix select above. The
+ * output is the k smallest by (key, index): what launch_topk writes whenever
+ * it does not end in its level-3 tie mode. stats (device, [2]) is added to:
+ * [0] rows the filter finished, [1] rows that fell back. */
+void launch_select(const float* dists, const int64_t* qoffs, int nq, int k,
+                   int32_t* out_slots, float* out_dists,
+                   unsigned long long* stats, hipStream_t stream);
+
 /* Map selected candidate slots to entry ids + apply the score transform
  * (scoreFromQuantized: raw/mul^2, then sqrt for orig-l2 — ivfflat/search.go:
  * 1062-1077). probe_lists/-offs describe each query's probed lists in rank
@@ -223,6 +234,19 @@ void launch_refine(int metric, const float* rows_f32, const float* queries,
 void launch_compose_select(const int32_t* sel2, const int32_t* rsel_slots,
                            int R, int k, int nq, int32_t* out,
                            hipStream_t stream);
+/* launch_refine -> launch_topk over [nq][R] -> launch_compose_select ->
+ * launch_gather as one kernel, same ids and distance bits; for the R and
+ * dpad refine_finish_applies admits (R <= 1024, LDS), k <= R */
+bool refine_finish_applies(int R, int dpad);
+void launch_refine_finish(int metric, const float* rows_f32,
+                          const float* queries, const float* qnorms, int dim,
+                          int dpad, int R, int nq, const int32_t* rsel_slots,
+                          const float* rsel_dists, const int32_t* probe_lists,
+                          const int64_t* probe_offs,
+                          const int64_t* list_slot_base,
+                          const int64_t* id_by_slot, int nprobe, int k,
+                          int do_sqrt, double inv_mul2, int64_t* out_ids,
+                          float* out_dists, hipStream_t stream);
 void launch_quantize_rows(bool uns, const float* in, int64_t nrows,
                           int in_stride, int dim, int dpad, float fmul,
                           float fadd, uint8_t* out, hipStream_t stream);

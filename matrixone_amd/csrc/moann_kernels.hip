@@ -30,6 +30,7 @@
 
 #include "moann_internal.h"
 #include "moann_scan_device.h"
+#include "moann_select_plan.h"
 
 namespace moann {
 
@@ -193,19 +194,63 @@ void launch_scan(int metric, ScanVariant v, const float* packed,
  * the tie-breaker, giving deterministic output. k <= 4096.
  * Replaces the bounded heaps of pkg/vectorindex/index.go:135-309 and the
  * cuVS select::topk stage. Padding: (-1, FLT_MAX) per cgo/cuvs/helper.h:160. */
-__global__ __launch_bounds__(256) void topk_kernel(
-    const float* __restrict__ dists, const int64_t* __restrict__ qoffs,
-    int64_t uniform_n, int k, int sortP,
+/* LDS of one radix-select block: 2 KiB of histogram and state, then the sort
+ * buffer */
+__host__ __device__ constexpr size_t topk_radix_lds(int sortP) {
+    return 2048 + (size_t)sortP * 8;
+}
+
+/* Tail of every block select: keys[0, nkeys) hold the collected
+ * (key << 32 | index) pairs, P >= nkeys is a power of two within the buffer.
+ * Pads to P, sorts ascending and writes the first m <= k entries of row q,
+ * (-1, FLT_MAX) behind them. Called by every thread of the block. */
+__device__ __forceinline__ void topk_sort_write(
+    uint64_t* keys, int nkeys, int P, int m, int q, int k,
     int32_t* __restrict__ out_slots, float* __restrict__ out_dists) {
-    extern __shared__ unsigned char smem[];
+    const int tid = threadIdx.x;
+    for (int i = nkeys + tid; i < P; i += blockDim.x) keys[i] = ~0ULL;
+    __syncthreads();
+
+    /* bitonic sort ascending over P u64 keys */
+    for (int ks = 2; ks <= P; ks <<= 1) {
+        for (int jj = ks >> 1; jj > 0; jj >>= 1) {
+            for (int i = tid; i < P; i += blockDim.x) {
+                const int l = i ^ jj;
+                if (l > i) {
+                    const uint64_t a = keys[i], b = keys[l];
+                    const bool up = (i & ks) == 0;
+                    if ((a > b) == up) { keys[i] = b; keys[l] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    for (int i = tid; i < k; i += blockDim.x) {
+        if (i < m) {
+            const uint64_t kv = keys[i];
+            out_slots[(int64_t)q * k + i] = (int32_t)(kv & 0xFFFFFFFFu);
+            out_dists[(int64_t)q * k + i] = u2f((uint32_t)(kv >> 32));
+        } else {
+            out_slots[(int64_t)q * k + i] = -1;
+            out_dists[(int64_t)q * k + i] = FLT_MAX;
+        }
+    }
+}
+
+/* One block's radix select of row q = dists[off, off+count) into row q of
+ * the outputs; smem holds topk_radix_lds(sortP) bytes and needs no set-up.
+ * Called by every thread of the block: topk_kernel's whole body, and the
+ * fallback of select_filter_kernel. */
+__device__ __forceinline__ void topk_radix_block(
+    const float* __restrict__ dists, int64_t off, int64_t count, int q, int k,
+    int sortP, unsigned char* smem, int32_t* __restrict__ out_slots,
+    float* __restrict__ out_dists) {
     uint32_t* hist = (uint32_t*)smem;                    /* 256 */
     uint32_t* ctr = hist + 256;                          /* n_lt, n_tie */
     uint32_t* st = ctr + 8;  /* prefix, c_sure, tieval, need_ties, done */
     uint64_t* keys = (uint64_t*)(smem + 2048);           /* [sortP] */
 
-    const int q = blockIdx.x;
-    const int64_t off = qoffs ? qoffs[q] : (int64_t)q * uniform_n;
-    const int64_t count = (qoffs ? qoffs[q + 1] : (int64_t)(q + 1) * uniform_n) - off;
     const int tid = threadIdx.x;
     const int m = (int)(count < (int64_t)k ? count : k);
     int nkeys;
@@ -311,40 +356,146 @@ __global__ __launch_bounds__(256) void topk_kernel(
 
     /* pad from the number of COLLECTED keys (group-collect gathers up to
      * sortP entries, more than k) and let the sort truncate to k */
-    for (int i = nkeys + tid; i < sortP; i += blockDim.x) keys[i] = ~0ULL;
-    __syncthreads();
+    topk_sort_write(keys, nkeys, sortP, m, q, k, out_slots, out_dists);
+}
 
-    /* bitonic sort ascending over sortP u64 keys */
-    for (int ks = 2; ks <= sortP; ks <<= 1) {
-        for (int jj = ks >> 1; jj > 0; jj >>= 1) {
-            for (int i = tid; i < sortP; i += blockDim.x) {
-                const int l = i ^ jj;
-                if (l > i) {
-                    const uint64_t a = keys[i], b = keys[l];
-                    const bool up = (i & ks) == 0;
-                    if ((a > b) == up) { keys[i] = b; keys[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+__global__ __launch_bounds__(256) void topk_kernel(
+    const float* __restrict__ dists, const int64_t* __restrict__ qoffs,
+    int64_t uniform_n, int k, int sortP,
+    int32_t* __restrict__ out_slots, float* __restrict__ out_dists) {
+    extern __shared__ unsigned char smem[];
+    const int q = blockIdx.x;
+    const int64_t off = qoffs ? qoffs[q] : (int64_t)q * uniform_n;
+    const int64_t count = (qoffs ? qoffs[q + 1] : (int64_t)(q + 1) * uniform_n) - off;
+    topk_radix_block(dists, off, count, q, k, sortP, smem, out_slots,
+                     out_dists);
+}
 
-    for (int i = tid; i < k; i += blockDim.x) {
-        if (i < m) {
-            const uint64_t kv = keys[i];
-            out_slots[(int64_t)q * k + i] = (int32_t)(kv & 0xFFFFFFFFu);
-            out_dists[(int64_t)q * k + i] = u2f((uint32_t)(kv >> 32));
-        } else {
-            out_slots[(int64_t)q * k + i] = -1;
-            out_dists[(int64_t)q * k + i] = FLT_MAX;
-        }
+/* ---------------- threshold-filter select for long ragged rows -----------
+ * The k smallest of a long row in ONE read (rule and constants:
+ * moann_select_plan.h). One block per row:
+ *  1. sample: m keys in runs spread evenly over the whole row (the candidate
+ *     buffer is ordered by probe rank, a prefix is no sample), one run of 16
+ *     per thread, kept in registers; the key of rank t among them, found by a bitwise
+ *     binary search on counts, is the threshold;
+ *  2. one pass of 16-byte loads, four in flight per thread; a key <= thr is
+ *     appended to the LDS buffer through one LDS counter (hits are under 1 %
+ *     of the row, so the counter is not contended);
+ *  3. >= k collected and no more than the capacity: sort them, write k. Any
+ *     other outcome runs topk_radix_block on the row: a bad threshold costs
+ *     time, never the result.
+ * Rows the plan does not admit (short, or k > SELECT_KMAX) go straight to
+ * the radix function. stats[0] counts filtered rows, stats[1] fallen-back
+ * ones. Output: the k smallest by (key, index), as topk_kernel. */
+__device__ __forceinline__ void select_hit(uint32_t u, uint32_t thr,
+                                           int64_t idx, uint32_t* cnt,
+                                           uint64_t* keys) {
+    if (u <= thr) {
+        const uint32_t pos = atomicAdd(cnt, 1u);
+        if (pos < (uint32_t)SELECT_CAPACITY)
+            keys[pos] = ((uint64_t)u << 32) | (uint32_t)idx;
     }
 }
 
-void launch_topk(const float* dists, const int64_t* qoffs, int64_t uniform_n,
-                 int nq, int k, int32_t* out_slots, float* out_dists,
-                 hipStream_t stream) {
-    if (nq == 0) return;
+__global__ __launch_bounds__(SELECT_THREADS) void select_filter_kernel(
+    const float* __restrict__ dists, const int64_t* __restrict__ qoffs,
+    int k, int sortP, int32_t* __restrict__ out_slots,
+    float* __restrict__ out_dists, unsigned long long* __restrict__ stats) {
+    extern __shared__ unsigned char smem[];
+    /* the radix function's layout, so the fallback reuses the same bytes:
+     * words of the first 2 KiB, then the key buffer */
+    uint32_t* cnt = (uint32_t*)smem;          /* collected keys            */
+    constexpr int NWAVES = SELECT_THREADS / WAVE;
+    static_assert(SELECT_THREADS % WAVE == 0 && 4 + 2 * NWAVES <= 512,
+                  "per-wave counts live in the 2 KiB state area");
+    uint32_t* wsum = cnt + 4;                 /* [2][NWAVES] wave counts   */
+    uint64_t* keys = (uint64_t*)(smem + 2048);/* [SELECT_CAPACITY]         */
+
+    const int q = blockIdx.x;
+    const int64_t off = qoffs[q];
+    const int64_t count = qoffs[q + 1] - off;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const SelectPlan plan = select_plan(count, k);
+    const float* row = dists + off;
+    bool radix = !plan.filter; /* block-uniform, like all that follows */
+    if (plan.filter) {
+        /* 1. sample -> threshold */
+        constexpr int SPT = SELECT_SAMPLE / SELECT_THREADS;
+        static_assert(SPT == SELECT_CLUSTER, "one sampled run per thread");
+        uint32_t s[SPT];
+#pragma unroll
+        for (int j = 0; j < SPT; ++j)
+            s[j] = f2u(row[select_sample_pos(count, SELECT_SAMPLE,
+                                             tid * SPT + j)]);
+        if (tid == 0) *cnt = 0;
+        /* thr = t-th smallest sample = the largest v with #(s < v) < t,
+         * built from the top bit down; one barrier per bit, on alternating
+         * slots */
+        uint32_t thr = 0;
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = thr | (1u << bit);
+            int c = 0;
+#pragma unroll
+            for (int j = 0; j < SPT; ++j) c += s[j] < cand;
+            for (int o = 32; o; o >>= 1) c += __shfl_down(c, o, 64);
+            uint32_t* slot = wsum + NWAVES * (bit & 1);
+            if (lane == 0) slot[wave] = (uint32_t)c;
+            __syncthreads();
+            uint32_t below = 0;
+#pragma unroll
+            for (int w = 0; w < NWAVES; ++w) below += slot[w];
+            if (below < (uint32_t)plan.t) thr = cand;
+        }
+
+        /* 2. one pass: scalar head up to 16-byte alignment, float4 body,
+         * scalar tail. dists is 16-byte aligned (a device allocation), off
+         * is not. */
+        int64_t head = (4 - (off & 3)) & 3;
+        if (head > count) head = count;
+        const int64_t nvec = (count - head) >> 2;
+        const int64_t tail0 = head + 4 * nvec;
+        if (tid < head) select_hit(f2u(row[tid]), thr, tid, cnt, keys);
+        if (tail0 + tid < count)
+            select_hit(f2u(row[tail0 + tid]), thr, tail0 + tid, cnt, keys);
+        const float4* body = (const float4*)(row + head);
+#define MOANN_SEL4(v, vi)                                                   \
+    select_hit(f2u((v).x), thr, head + 4 * (vi), cnt, keys);                \
+    select_hit(f2u((v).y), thr, head + 4 * (vi) + 1, cnt, keys);            \
+    select_hit(f2u((v).z), thr, head + 4 * (vi) + 2, cnt, keys);            \
+    select_hit(f2u((v).w), thr, head + 4 * (vi) + 3, cnt, keys);
+        int64_t i = tid;
+        const int64_t step = SELECT_THREADS;
+        for (; i + 3 * step < nvec; i += 4 * step) {
+            const float4 v0 = body[i], v1 = body[i + step];
+            const float4 v2 = body[i + 2 * step], v3 = body[i + 3 * step];
+            MOANN_SEL4(v0, i) MOANN_SEL4(v1, i + step)
+            MOANN_SEL4(v2, i + 2 * step) MOANN_SEL4(v3, i + 3 * step)
+        }
+        for (; i < nvec; i += step) {
+            const float4 v = body[i];
+            MOANN_SEL4(v, i)
+        }
+#undef MOANN_SEL4
+        __syncthreads();
+
+        /* 3. finish (count >= SELECT_MIN_COUNT > k here) */
+        const uint32_t got = *cnt;
+        radix = got < (uint32_t)k || got > (uint32_t)SELECT_CAPACITY;
+        if (tid == 0) atomicAdd(&stats[radix ? 1 : 0], 1ull);
+        if (!radix) {
+            int P = 1;
+            while (P < (int)got) P <<= 1;
+            topk_sort_write(keys, (int)got, P, k, q, k, out_slots, out_dists);
+        }
+        __syncthreads(); /* every thread has read cnt */
+    }
+    if (radix)
+        topk_radix_block(dists, off, count, q, k, sortP, smem, out_slots,
+                         out_dists);
+}
+
+/* sort buffer of the radix select for this k */
+static int topk_sort_size(int k) {
     int sortP = 1;
     while (sortP < k) sortP <<= 1;
     /* A larger sort buffer makes the group-collect exit fire at level 0
@@ -352,10 +503,30 @@ void launch_topk(const float* dists, const int64_t* qoffs, int64_t uniform_n,
      * reads instead of 3 for the big per-query candidate selections. The
      * extra bitonic work (1024 u64 keys) is microseconds per block; LDS
      * 2048+8*1024 = 10 KB still keeps several blocks per CU. */
-    if (sortP < 1024) sortP = 1024;
-    const size_t shmem = 2048 + (size_t)sortP * 8;
-    hipLaunchKernelGGL(topk_kernel, dim3(nq), dim3(256), shmem, stream,
-                       dists, qoffs, uniform_n, k, sortP, out_slots, out_dists);
+    return sortP < 1024 ? 1024 : sortP;
+}
+
+void launch_topk(const float* dists, const int64_t* qoffs, int64_t uniform_n,
+                 int nq, int k, int32_t* out_slots, float* out_dists,
+                 hipStream_t stream) {
+    if (nq == 0) return;
+    const int sortP = topk_sort_size(k);
+    hipLaunchKernelGGL(topk_kernel, dim3(nq), dim3(256),
+                       topk_radix_lds(sortP), stream, dists, qoffs, uniform_n,
+                       k, sortP, out_slots, out_dists);
+}
+
+void launch_select(const float* dists, const int64_t* qoffs, int nq, int k,
+                   int32_t* out_slots, float* out_dists,
+                   unsigned long long* stats, hipStream_t stream) {
+    if (nq == 0) return;
+    const int sortP = topk_sort_size(k);
+    /* 18 KiB at k <= SELECT_KMAX: eight blocks per CU */
+    const size_t shmem = std::max(topk_radix_lds(sortP),
+                                  topk_radix_lds(SELECT_CAPACITY));
+    hipLaunchKernelGGL(select_filter_kernel, dim3(nq), dim3(SELECT_THREADS),
+                       shmem, stream, dists, qoffs, k, sortP, out_slots,
+                       out_dists, stats);
 }
 
 /* ------------------------------ gather ----------------------------------- */
@@ -889,6 +1060,196 @@ void launch_compose_select(const int32_t* sel2, const int32_t* rsel_slots,
     hipLaunchKernelGGL(compose_select_kernel,
                        dim3((uint32_t)((total + 255) / 256)), dim3(256), 0,
                        stream, sel2, rsel_slots, R, k, total, out);
+}
+
+/* ---------------- fused refine tail (R <= REFINE_FINISH_RMAX) ------------
+ * refine_kernel -> topk_kernel over [nq][R] -> compose_select_kernel ->
+ * gather_kernel in one block per query:
+ *  1. threads c < R resolve candidate position -> global slot, once, into
+ *     LDS (-1: padding, or a byte distance of FLT_MAX);
+ *  2. a wave takes candidates four at a time and loads from all four rows
+ *     before it accumulates, so four rows are in flight per wave where
+ *     refine_kernel has one behind a chain of dependent loads. Each
+ *     candidate keeps refine_kernel's arithmetic: lane l sums dims l, l+64,
+ *     ... in ascending order, the same shfl tree, the same finish — the
+ *     exact distances are bit-identical;
+ *  3. bitonic sort of (f2u(dist) << 32 | c) over next_pow2(R) keys: what
+ *     topk_kernel returns for a row of R <= 1024 values;
+ *  4. thread i < k writes id and transformed distance, gather_kernel's
+ *     padding rule.
+ * LDS: [dpad] f32 query, [P] u64 keys, [R] i64 slots. */
+constexpr int REFINE_FINISH_RMAX = 1024;
+
+template <int METRIC>
+__global__ __launch_bounds__(256) void refine_finish_kernel(
+    const float* __restrict__ rows_f32, const float* __restrict__ queries,
+    const float* __restrict__ qnorms, int dim, int dpad, int R, int P,
+    const int32_t* __restrict__ rsel_slots,
+    const float* __restrict__ rsel_dists,
+    const int32_t* __restrict__ probe_lists,
+    const int64_t* __restrict__ probe_offs,
+    const int64_t* __restrict__ list_slot_base,
+    const int64_t* __restrict__ id_by_slot, int nprobe, int k, int do_sqrt,
+    double inv_mul2, int64_t* __restrict__ out_ids,
+    float* __restrict__ out_dists) {
+    extern __shared__ unsigned char rf_smem[];
+    uint64_t* keys = (uint64_t*)rf_smem;         /* [P]    */
+    int64_t* slots = (int64_t*)(keys + P);       /* [R]    */
+    float* ldsq = (float*)(slots + R);           /* [dpad] */
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const float* qv = queries + (int64_t)q * dpad;
+    for (int e = tid; e < dpad; e += blockDim.x) ldsq[e] = qv[e];
+
+    /* 1. candidate position -> (probed list, local row) -> global slot */
+    const int64_t* offs = probe_offs + (int64_t)q * (nprobe + 1);
+    for (int c = tid; c < R; c += blockDim.x) {
+        const int64_t idx = (int64_t)q * R + c;
+        const int32_t pos = rsel_slots[idx];
+        int64_t slot = -1;
+        if (pos >= 0 && rsel_dists[idx] != FLT_MAX) {
+            int lo = 0, hi = nprobe - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (offs[mid] <= pos) lo = mid; else hi = mid - 1;
+            }
+            const int32_t list = probe_lists[(int64_t)q * nprobe + lo];
+            slot = list_slot_base[list] + (pos - offs[lo]);
+        }
+        slots[c] = slot;
+    }
+    for (int c = R + tid; c < P; c += blockDim.x) keys[c] = ~0ULL;
+    __syncthreads();
+
+    /* 2. exact distances, four candidates per wave step */
+    for (int c0 = wave * 4; c0 < R; c0 += 16) {
+        const float* row[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t slot = c0 + j < R ? slots[c0 + j] : -1;
+            row[j] = slot < 0 ? nullptr : rows_f32 + slot * (int64_t)dim;
+        }
+        float acc[4] = {0.f, 0.f, 0.f, 0.f}, rn[4] = {0.f, 0.f, 0.f, 0.f};
+        /* four 64-dim steps of four rows: 16 loads issued, then summed */
+        for (int t0 = lane; t0 < dim; t0 += 256) {
+            float x[4][4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    x[s][j] = (t0 + 64 * s < dim && row[j])
+                                  ? row[j][t0 + 64 * s] : 0.f;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int t = t0 + 64 * s;
+                if (t < dim) {
+                    const float qq = ldsq[t];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float xv = x[s][j];
+                        if (METRIC == KM_L2SQ) {
+                            const float e = xv - qq;
+                            acc[j] = fmaf(e, e, acc[j]);
+                        } else if (METRIC == KM_IP || METRIC == KM_COS) {
+                            acc[j] = fmaf(xv, qq, acc[j]);
+                            if (METRIC == KM_COS)
+                                rn[j] = fmaf(xv, xv, rn[j]);
+                        } else {
+                            acc[j] += fabsf(xv - qq);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float a = acc[j], r = rn[j];
+            for (int off = 32; off; off >>= 1) {
+                a += __shfl_down(a, off, 64);
+                if (METRIC == KM_COS) r += __shfl_down(r, off, 64);
+            }
+            if (lane == 0 && c0 + j < R) { /* qnorms is null unless cos */
+                float dist = FLT_MAX;
+                if (row[j]) {
+                    if (METRIC == KM_IP) dist = -a;
+                    else if (METRIC == KM_COS)
+                        dist = mo_cos_distance(a, r, qnorms[q]);
+                    else dist = a;
+                }
+                keys[c0 + j] = ((uint64_t)f2u(dist) << 32) | (uint32_t)(c0 + j);
+            }
+        }
+    }
+    __syncthreads();
+
+    /* 3. sort, 4. write */
+    for (int ks = 2; ks <= P; ks <<= 1) {
+        for (int jj = ks >> 1; jj > 0; jj >>= 1) {
+            for (int i = tid; i < P; i += blockDim.x) {
+                const int l = i ^ jj;
+                if (l > i) {
+                    const uint64_t a = keys[i], b = keys[l];
+                    const bool up = (i & ks) == 0;
+                    if ((a > b) == up) { keys[i] = b; keys[l] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < k; i += blockDim.x) {
+        const int64_t o = (int64_t)q * k + i;
+        int64_t slot = -1;
+        float dist = FLT_MAX;
+        if (i < R) {
+            const uint64_t kv = keys[i];
+            slot = slots[(uint32_t)kv];
+            dist = u2f((uint32_t)(kv >> 32));
+        }
+        /* FLT_MAX marks padding AND membership-filtered rows */
+        if (slot < 0 || dist == FLT_MAX) {
+            out_ids[o] = -1; out_dists[o] = FLT_MAX;
+        } else {
+            out_ids[o] = id_by_slot[slot];
+            out_dists[o] = transform_score_dev(dist, do_sqrt, inv_mul2);
+        }
+    }
+}
+
+static size_t refine_finish_lds(int R, int dpad) {
+    int P = 1;
+    while (P < R) P <<= 1;
+    return (size_t)P * 8 + (size_t)R * 8 + (size_t)dpad * 4;
+}
+
+bool refine_finish_applies(int R, int dpad) {
+    return R <= REFINE_FINISH_RMAX && refine_finish_lds(R, dpad) <= 64 * 1024;
+}
+
+void launch_refine_finish(int metric, const float* rows_f32,
+                          const float* queries, const float* qnorms, int dim,
+                          int dpad, int R, int nq, const int32_t* rsel_slots,
+                          const float* rsel_dists, const int32_t* probe_lists,
+                          const int64_t* probe_offs,
+                          const int64_t* list_slot_base,
+                          const int64_t* id_by_slot, int nprobe, int k,
+                          int do_sqrt, double inv_mul2, int64_t* out_ids,
+                          float* out_dists, hipStream_t stream) {
+    if (!nq) return;
+    if (!refine_finish_applies(R, dpad) || k > R)
+        throw std::logic_error("launch_refine_finish: R " + std::to_string(R) +
+                               " k " + std::to_string(k) + " dpad " +
+                               std::to_string(dpad));
+    int P = 1;
+    while (P < R) P <<= 1;
+    const size_t shmem = refine_finish_lds(R, dpad);
+    with_metric(metric, [&](auto m) {
+        hipLaunchKernelGGL(refine_finish_kernel<decltype(m)::value>, dim3(nq),
+                           dim3(256), shmem, stream, rows_f32, queries, qnorms,
+                           dim, dpad, R, P, rsel_slots, rsel_dists,
+                           probe_lists, probe_offs, list_slot_base,
+                           id_by_slot, nprobe, k, do_sqrt, inv_mul2, out_ids,
+                           out_dists);
+    });
 }
 
 /* -------------------------- quantized (int8/uint8) scan ------------------

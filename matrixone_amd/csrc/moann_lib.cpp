@@ -34,6 +34,7 @@
 #include "../../include/moann.h"
 #include "moann_host_common.h"
 #include "moann_kmeans_plan.h"
+#include "moann_select_plan.h"
 
 namespace {
 
@@ -93,6 +94,7 @@ struct SearchCtx {
         uint32_t limit = 0, probe = 0;
         ScanChoice scan {};
         bool refine = false;            /* two-stage scan active            */
+        bool outputs_written = false;   /* fused refine tail filled w_out_* */
         const float* d_q = nullptr;     /* [nq][dpad] padded queries        */
         const float* d_qn = nullptr;    /* [nq] |q|^2, when a stage needs it */
     } call;
@@ -122,6 +124,8 @@ struct SearchCtx {
     }
 };
 
+const ScanOverrides& scan_overrides(); /* below */
+
 struct IvfIndex {
     /* config */
     int device = 0;
@@ -143,6 +147,10 @@ struct IvfIndex {
     ByteImageLayout rq_layout = ByteImageLayout::ROWS16; /* its byte order */
     int32_t* d_rownorm_rq = nullptr;
     double rq_mul = 1.0, rq_add = 0.0;
+    /* selection and refine tail (moann_ivf_flat_set_refine_tail): legacy =
+     * radix select for every selection and the four-kernel refine tail */
+    bool refine_tail_legacy = scan_overrides().refine_tail_legacy;
+    unsigned long long* d_select_stats = nullptr; /* [2] filtered, fallback */
     bool built = false, started = false;
 
     hipStream_t stream = nullptr;
@@ -253,7 +261,8 @@ struct IvfIndex {
                        (void*)d_cent_rows, (void*)d_cnorms, (void*)d_packed_q,
                        (void*)d_rownorm_q, (void*)d_rows_f32,
                        (void*)d_packed_rq, (void*)d_rownorm_rq,
-                       (void*)d_id_by_slot, (void*)d_list_slot_base})
+                       (void*)d_id_by_slot, (void*)d_list_slot_base,
+                       (void*)d_select_stats})
             if (p) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -411,8 +420,10 @@ const ScanOverrides& scan_overrides() {
     static const ScanOverrides ov = [] {
         const char *sc = getenv("MOANN_SCAN"), *bq = getenv("MOANN_BYTE_QT"),
                    *cg = getenv("MOANN_CHUNKG"),
-                   *bm = getenv("MOANN_BYTE_MFMA");
+                   *bm = getenv("MOANN_BYTE_MFMA"),
+                   *rt = getenv("MOANN_REFINE_TAIL");
         ScanOverrides o;
+        o.refine_tail_legacy = rt && strcmp(rt, "legacy") == 0;
         o.generic_f32 = sc && strcmp(sc, "generic") == 0;
         o.byte_qt8 = bq && atoi(bq) == 8;
         o.chunk_g = cg ? atoi(cg) : 0;
@@ -574,8 +585,16 @@ void scan_lists(IvfIndex* ix, SearchCtx* cx, const uint32_t* filter_words) {
 
 /* 5. per-query top-limit over the candidates; for the two-stage scan: top-R
  * by byte distance -> exact f32 re-rank -> top-limit -> candidate slots */
+int score_sqrt(const IvfIndex* ix) {
+    return ix->metric == DistanceType_L2SqrtExpanded;
+}
+double score_inv_mul2(const IvfIndex* ix) {
+    return (ix->quant_mul != 0.0 && ix->quant_mul != 1.0)
+               ? 1.0 / (ix->quant_mul * ix->quant_mul) : 1.0;
+}
+
 void select_candidates(IvfIndex* ix, SearchCtx* cx) {
-    const SearchCtx::Call& c = cx->call;
+    SearchCtx::Call& c = cx->call;
     const int dpad = (int)ix->dpad, nq = (int)c.nq, limit = (int)c.limit;
     const hipStream_t s = cx->stream;
     upload_vector(cx->w_qoffs, cx->offs.qoffs, s);
@@ -583,15 +602,50 @@ void select_candidates(IvfIndex* ix, SearchCtx* cx) {
     upload_vector(cx->w_probe_offs, cx->offs.probe_offs, s);
     cx->w_sel_slots.ensure((size_t)c.nq * limit * 4);
     cx->w_sel_dists.ensure((size_t)c.nq * limit * 4);
+    const bool legacy = ix->refine_tail_legacy;
+    if (!legacy && !ix->d_select_stats) {
+        HIP_CHECK(hipMalloc(&ix->d_select_stats, 16));
+        HIP_CHECK(hipMemset(ix->d_select_stats, 0, 16)); /* once */
+    }
+    /* the ragged selection: one read against a sampled threshold, or the
+     * radix select under the legacy switch */
+    const auto select_ragged = [&](int k, int32_t* slots, float* dists) {
+        if (legacy)
+            launch_topk(cx->w_cand.as<float>(), cx->w_qoffs.as<int64_t>(), 0,
+                        nq, k, slots, dists, s);
+        else
+            launch_select(cx->w_cand.as<float>(), cx->w_qoffs.as<int64_t>(),
+                          nq, k, slots, dists, ix->d_select_stats, s);
+    };
+    c.outputs_written = false;
     HIP_CHECK(hipEventRecord(cx->ev[4], s));
     if (c.refine) {
         const int R = std::max<int>(limit, ix->refine_depth);
         cx->w_rsel_slots.ensure((size_t)c.nq * R * 4);
         cx->w_rsel_dists.ensure((size_t)c.nq * R * 4);
-        launch_topk(cx->w_cand.as<float>(), cx->w_qoffs.as<int64_t>(), 0, nq,
-                    R, cx->w_rsel_slots.as<int32_t>(),
-                    cx->w_rsel_dists.as<float>(), s);
+        select_ragged(R, cx->w_rsel_slots.as<int32_t>(),
+                      cx->w_rsel_dists.as<float>());
         KCHECK("refine-topR");
+        if (!legacy && refine_finish_applies(R, dpad)) {
+            /* exact re-rank, top-limit, ids and score transform in one
+             * kernel: gather_results only copies */
+            const size_t n = (size_t)c.nq * limit;
+            cx->w_out_ids.ensure(n * 8);
+            cx->w_out_dists.ensure(n * 4);
+            launch_refine_finish(
+                ix->kmetric, ix->d_rows_f32, c.d_q, c.d_qn, (int)ix->dim,
+                dpad, R, nq, cx->w_rsel_slots.as<int32_t>(),
+                cx->w_rsel_dists.as<float>(),
+                cx->w_probe_lists.as<int32_t>(),
+                cx->w_probe_offs.as<int64_t>(), ix->d_list_slot_base,
+                ix->d_id_by_slot, (int)c.probe, limit, score_sqrt(ix),
+                score_inv_mul2(ix), cx->w_out_ids.as<int64_t>(),
+                cx->w_out_dists.as<float>(), s);
+            KCHECK("refine-finish");
+            c.outputs_written = true;
+            HIP_CHECK(hipEventRecord(cx->ev[5], s));
+            return;
+        }
         cx->w_refined.ensure((size_t)c.nq * R * 4);
         launch_refine(ix->kmetric, ix->d_rows_f32, c.d_q, c.d_qn,
                       (int)ix->dim, dpad, R, nq,
@@ -610,34 +664,33 @@ void select_candidates(IvfIndex* ix, SearchCtx* cx) {
                               cx->w_sel_slots.as<int32_t>(), s);
         KCHECK("refine-compose");
     } else {
-        launch_topk(cx->w_cand.as<float>(), cx->w_qoffs.as<int64_t>(), 0, nq,
-                    limit, cx->w_sel_slots.as<int32_t>(),
-                    cx->w_sel_dists.as<float>(), s);
+        select_ragged(limit, cx->w_sel_slots.as<int32_t>(),
+                      cx->w_sel_dists.as<float>());
         KCHECK("cand-topk");
     }
     HIP_CHECK(hipEventRecord(cx->ev[5], s));
 }
 
-/* 6. id gather + score transform, then D2H through the ctx's pinned bounce
- * (pageable-async degrades to a host-blocking copy on ROCm, which would
- * serialize the pipeline) */
+/* 6. id gather + score transform (unless the fused refine tail has written
+ * them), then D2H through the ctx's pinned bounce (pageable-async degrades
+ * to a host-blocking copy on ROCm, which would serialize the pipeline) */
 void gather_results(IvfIndex* ix, SearchCtx* cx) {
     const SearchCtx::Call& c = cx->call;
     const size_t n = (size_t)c.nq * c.limit;
     const hipStream_t s = cx->stream;
-    const int do_sqrt = ix->metric == DistanceType_L2SqrtExpanded;
-    const double inv_mul2 =
-        (ix->quant_mul != 0.0 && ix->quant_mul != 1.0)
-            ? 1.0 / (ix->quant_mul * ix->quant_mul) : 1.0;
-    cx->w_out_ids.ensure(n * 8);
-    cx->w_out_dists.ensure(n * 4);
-    launch_gather(cx->w_sel_slots.as<int32_t>(), cx->w_sel_dists.as<float>(),
-                  cx->w_probe_lists.as<int32_t>(),
-                  cx->w_probe_offs.as<int64_t>(), ix->d_list_slot_base,
-                  ix->d_id_by_slot, (int)c.probe, (int)c.nq, (int)c.limit,
-                  do_sqrt, inv_mul2, cx->w_out_ids.as<int64_t>(),
-                  cx->w_out_dists.as<float>(), s);
-    KCHECK("gather");
+    if (!c.outputs_written) {
+        cx->w_out_ids.ensure(n * 8);
+        cx->w_out_dists.ensure(n * 4);
+        launch_gather(cx->w_sel_slots.as<int32_t>(),
+                      cx->w_sel_dists.as<float>(),
+                      cx->w_probe_lists.as<int32_t>(),
+                      cx->w_probe_offs.as<int64_t>(), ix->d_list_slot_base,
+                      ix->d_id_by_slot, (int)c.probe, (int)c.nq, (int)c.limit,
+                      score_sqrt(ix), score_inv_mul2(ix),
+                      cx->w_out_ids.as<int64_t>(),
+                      cx->w_out_dists.as<float>(), s);
+        KCHECK("gather");
+    }
     cx->ensure_hout(n * 12);
     int64_t* ho_ids = (int64_t*)cx->h_out;
     float* ho_dists = (float*)(ho_ids + n);
@@ -1936,6 +1989,124 @@ void moann_ivf_flat_kmeans_stats(gpu_ivf_flat_c h, double* train_ms,
     }
 }
 
+void moann_ivf_flat_select_stats(gpu_ivf_flat_c h, uint64_t* filtered,
+                                 uint64_t* fallback, void* errmsg) {
+    try {
+        auto ix = IX(h);
+        if (!ix) throw std::runtime_error("null index");
+        std::lock_guard<std::mutex> lk(ix->mu);
+        /* the main lists and the tail of extended rows, whose searches count
+         * into the tail index's own counter */
+        unsigned long long sum[2] = {0, 0};
+        for (IvfIndex* part : {ix, ix->tail.get()}) {
+            if (!part || !part->d_select_stats) continue;
+            unsigned long long st[2];
+            HIP_CHECK(hipSetDevice(part->device));
+            /* a blocking copy: every search submitted so far has counted */
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(st, part->d_select_stats, sizeof st,
+                                hipMemcpyDeviceToHost));
+            sum[0] += st[0];
+            sum[1] += st[1];
+        }
+        if (filtered) *filtered = sum[0];
+        if (fallback) *fallback = sum[1];
+    } catch (const std::exception& e) {
+        set_errmsg(errmsg, "moann_ivf_flat_select_stats", e.what());
+    }
+}
+
+void moann_ivf_flat_set_refine_tail(gpu_ivf_flat_c h, int legacy,
+                                    void* errmsg) {
+    try {
+        auto ix = IX(h);
+        if (!ix) throw std::runtime_error("null index");
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->refine_tail_legacy = legacy != 0;
+        if (ix->tail) ix->tail->refine_tail_legacy = legacy != 0;
+    } catch (const std::exception& e) {
+        set_errmsg(errmsg, "moann_ivf_flat_set_refine_tail", e.what());
+    }
+}
+
+void moann_select_plan(int64_t count, int32_t k, int32_t* filter,
+                       int32_t* sample, int32_t* rank, int32_t* capacity,
+                       int64_t* min_count, int32_t* kmax) {
+    const SelectPlan p = select_plan(count, k);
+    if (filter) *filter = p.filter;
+    if (sample) *sample = p.m;
+    if (rank) *rank = p.t;
+    if (capacity) *capacity = SELECT_CAPACITY;
+    if (min_count) *min_count = SELECT_MIN_COUNT;
+    if (kmax) *kmax = SELECT_KMAX;
+}
+
+void moann_select_sample_positions(int64_t count, int32_t k, int64_t* out) {
+    const SelectPlan p = select_plan(count, k);
+    for (int i = 0; p.filter && i < p.m; ++i)
+        out[i] = select_sample_pos(count, p.m, i);
+}
+
+void moann_select_topk(const float* dists, const int64_t* qoffs, int64_t nq,
+                       int32_t k, int32_t mode, int32_t* out_slots,
+                       float* out_dists, uint64_t* fallbacks, double* kernel_ms,
+                       void* errmsg) {
+    try {
+        if (nq < 0 || nq > INT32_MAX || k < 1 || k > 4096 ||
+            (mode != 0 && mode != 1))
+            throw std::runtime_error("bad nq, k or mode");
+        if (fallbacks) *fallbacks = 0;
+        if (kernel_ms) *kernel_ms = 0.0;
+        if (nq == 0) return;
+        for (int64_t q = 0; q < nq; ++q)
+            if (qoffs[q] < 0 || qoffs[q + 1] < qoffs[q] ||
+                qoffs[q + 1] - qoffs[q] > UINT32_MAX)
+                throw std::runtime_error("qoffs must ascend from >= 0");
+        const size_t total = (size_t)qoffs[nq], no = (size_t)nq * k;
+        DevBuf d_d, d_o, d_s, d_od, d_st;
+        d_d.ensure(std::max<size_t>(1, total) * 4);
+        d_o.ensure((size_t)(nq + 1) * 8);
+        d_s.ensure(no * 4);
+        d_od.ensure(no * 4);
+        d_st.ensure(16);
+        HIP_CHECK(hipMemcpy(d_d.ptr, dists, total * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_o.ptr, qoffs, (size_t)(nq + 1) * 8,
+                            hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(d_st.ptr, 0, 16));
+        struct Events { /* destroyed on every way out */
+            hipEvent_t e[2] = {nullptr, nullptr};
+            ~Events() {
+                for (hipEvent_t x : e)
+                    if (x) (void)hipEventDestroy(x);
+            }
+        } ev;
+        HIP_CHECK(hipEventCreate(&ev.e[0]));
+        HIP_CHECK(hipEventCreate(&ev.e[1]));
+        HIP_CHECK(hipEventRecord(ev.e[0], nullptr));
+        if (mode == 1)
+            launch_select(d_d.as<float>(), d_o.as<int64_t>(), (int)nq, k,
+                          d_s.as<int32_t>(), d_od.as<float>(),
+                          d_st.as<unsigned long long>(), nullptr);
+        else
+            launch_topk(d_d.as<float>(), d_o.as<int64_t>(), 0, (int)nq, k,
+                        d_s.as<int32_t>(), d_od.as<float>(), nullptr);
+        HIP_CHECK(hipEventRecord(ev.e[1], nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        KCHECK("select-topk");
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        unsigned long long st[2];
+        HIP_CHECK(hipMemcpy(out_slots, d_s.ptr, no * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out_dists, d_od.ptr, no * 4,
+                            hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(st, d_st.ptr, 16, hipMemcpyDeviceToHost));
+        if (fallbacks) *fallbacks = st[1];
+        if (kernel_ms) *kernel_ms = ms;
+    } catch (const std::exception& e) {
+        set_errmsg(errmsg, "moann_select_topk", e.what());
+    }
+}
+
 void moann_brute_force_search(const float* dataset, uint64_t count,
                               uint32_t dimension, distance_type_t metric,
                               const int64_t* ids, const float* queries,
@@ -2116,6 +2287,7 @@ static void rebuild_tail(IvfIndex* ix) {
     chk("tail set_assignments");
     gpu_ivf_flat_build(th, &inner);
     chk("tail build");
+    tix->refine_tail_legacy = ix->refine_tail_legacy;
     ix->tail = std::move(tix);
     /* re-apply soft deletes that target tail rows */
     for (int64_t id : ix->tail_deleted) {

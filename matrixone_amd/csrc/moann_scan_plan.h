@@ -66,6 +66,10 @@ struct ScanOverrides {
     int chunk_g = 0;          /* MOANN_CHUNKG: list chunk groups, 0 = 8   */
     bool byte_mfma_off = false; /* MOANN_BYTE_MFMA=0: refine image stays in
                                    ROWS16, scanned by the dot kernel      */
+    bool refine_tail_legacy = false; /* MOANN_REFINE_TAIL=legacy: radix
+                                   select + four-kernel refine tail; an
+                                   index starts from it
+                                   (moann_ivf_flat_set_refine_tail)       */
 };
 
 struct ScanChoice { /* the list scan's and the centroid-rank scan's */

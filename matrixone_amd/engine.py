@@ -175,6 +175,20 @@ def lib() -> ct.CDLL:
     L.moann_ivf_flat_result_wait.argtypes = [ct.c_void_p, ct.c_void_p]
     L.moann_ivf_flat_enable_refine.argtypes = [ct.c_void_p, ct.c_uint32,
                                                ct.c_void_p]
+    L.moann_ivf_flat_set_refine_tail.argtypes = [ct.c_void_p, ct.c_int,
+                                                 ct.c_void_p]
+    L.moann_ivf_flat_select_stats.argtypes = [
+        ct.c_void_p, ct.POINTER(ct.c_uint64), ct.POINTER(ct.c_uint64),
+        ct.c_void_p]
+    L.moann_select_topk.argtypes = [
+        ct.c_void_p, ct.c_void_p, ct.c_int64, ct.c_int32, ct.c_int32,
+        ct.c_void_p, ct.c_void_p, ct.POINTER(ct.c_uint64),
+        ct.POINTER(ct.c_double), ct.c_void_p]
+    L.moann_select_plan.argtypes = [
+        ct.c_int64, ct.c_int32] + [ct.POINTER(ct.c_int32)] * 4 + [
+        ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int32)]
+    L.moann_select_sample_positions.argtypes = [ct.c_int64, ct.c_int32,
+                                                ct.c_void_p]
     L.moann_docfilter_eval.restype = ct.c_int
     L.moann_docfilter_eval.argtypes = [
         ct.c_int, ct.c_void_p, ct.c_uint64, ct.c_void_p, ct.c_uint64,
@@ -672,6 +686,25 @@ class IvfFlatIndex:
         lib().moann_ivf_flat_enable_refine(self._h, depth, err.ref)
         err.check("enable_refine")
 
+    def set_refine_tail(self, legacy: bool):
+        """legacy=True: radix select and the four-kernel refine tail;
+        False (the default unless MOANN_REFINE_TAIL=legacy): threshold-filter
+        select and the fused tail (moann_ivf_flat_set_refine_tail)."""
+        err = _Err()
+        lib().moann_ivf_flat_set_refine_tail(self._h, int(bool(legacy)),
+                                             err.ref)
+        err.check("set_refine_tail")
+
+    def select_stats(self) -> dict:
+        """Queries the threshold filter finished / handed back to the radix
+        select, over the life of the index (moann_ivf_flat_select_stats)."""
+        f, b = ct.c_uint64(0), ct.c_uint64(0)
+        err = _Err()
+        lib().moann_ivf_flat_select_stats(self._h, ct.byref(f), ct.byref(b),
+                                          err.ref)
+        err.check("select_stats")
+        return {"filtered": f.value, "fallback": b.value}
+
     def preds_bitset(self, cols_meta, columns, preds_json: str,
                      nulls=None) -> np.ndarray:
         """Slot bitset from a planner predicate list over ADD-order column
@@ -844,6 +877,51 @@ def brute_force_search(dataset, queries, k: int, metric: str = "l2sq",
         out_ids.ctypes.data, out_dists.ctypes.data, err.ref)
     err.check("brute_force_search")
     return out_ids, out_dists
+
+
+SELECT_MODES = {"radix": 0, "filter": 1}
+
+
+def select_plan(count: int, k: int) -> dict:
+    """The threshold filter's rule for a row of `count` values at this k
+    (moann_select_plan, no GPU needed): `filter` whether the row takes the
+    filter path, `sample` the number of sampled keys, `rank` of the sampled
+    key that becomes the threshold (1-based), and the constants `capacity`,
+    `min_count`, `kmax`."""
+    f, m, t, cap, kmax = (ct.c_int32(0) for _ in range(5))
+    mn = ct.c_int64(0)
+    lib().moann_select_plan(count, k, ct.byref(f), ct.byref(m), ct.byref(t),
+                            ct.byref(cap), ct.byref(mn), ct.byref(kmax))
+    return {"filter": bool(f.value), "sample": m.value, "rank": t.value,
+            "capacity": cap.value, "min_count": mn.value, "kmax": kmax.value}
+
+
+def select_sample_positions(count: int, k: int) -> np.ndarray:
+    """Row positions the filter samples in a row of `count` values at this
+    k; empty when the row does not take the filter path."""
+    p = select_plan(count, k)
+    out = np.zeros(p["sample"] if p["filter"] else 0, dtype=np.int64)
+    lib().moann_select_sample_positions(count, k, out.ctypes.data)
+    return out
+
+
+def select_topk(dists, qoffs, k: int, mode: str = "filter"):
+    """The ragged per-row selection kernels alone (moann_select_topk): row q
+    is dists[qoffs[q]:qoffs[q+1]]. Returns (slots [nq][k] int32, dists
+    [nq][k] f32, fallbacks, kernel_ms)."""
+    dists = np.ascontiguousarray(dists, dtype=np.float32)
+    qoffs = np.ascontiguousarray(qoffs, dtype=np.int64)
+    nq = qoffs.shape[0] - 1
+    out_s = np.empty((nq, k), dtype=np.int32)
+    out_d = np.empty((nq, k), dtype=np.float32)
+    fb, ms = ct.c_uint64(0), ct.c_double(0)
+    err = _Err()
+    lib().moann_select_topk(dists.ctypes.data, qoffs.ctypes.data, nq, k,
+                            SELECT_MODES[mode], out_s.ctypes.data,
+                            out_d.ctypes.data, ct.byref(fb), ct.byref(ms),
+                            err.ref)
+    err.check("select_topk")
+    return out_s, out_d, int(fb.value), float(ms.value)
 
 
 BF_MODES = {"auto": 0, "fused": 1, "gemm": 2}
